@@ -9,12 +9,17 @@ replacement, the CFG-batched B = 2 DiT forward on the 2B net at latent [16, 31, 
 L = 109 120 tokens, GT-frame velocity replacement + CFG, fused UniPC update). The encode, the setup
 and the 121-frame decode are timed once each in the same run (barrier + synchronize around each);
   modeled = frames / (t_encode + t_setup + evals_per_video * t_step + t_decode)
-and, by default, one whole video is then timed end to end (encode + every evaluation + decode, barrier +
-synchronize around it): value = frames / t_whole_video (--no-whole-video: value = the modeled figure).
+A plain run stops there: value = the modeled figure (value_method says so), ms_per_step = t_step.
 Synthetic data: seeded random weights with the 2B shapes, a random conditioning image, N(0, 1) text
-embeddings [1, 512, 100352]. bf16 compute.
+embeddings [1, 512, 100352]; the same arguments give the same inputs in every run. bf16 compute.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+--dump-outputs DIR: after the timed steps, what the last one left its caller (SamplingRun.latents(), the fp32 latent
+state [1, 16, 31, 88, 160]) is written as DIR/latents.npy (float32, 28 MB at the metric geometry).
+--full: everything else the benchmark measures, each a run of its own after the plain part: one whole video timed
+end to end (encode + every evaluation + decode, barrier + synchronize around it; value = frames / t_whole_video
+then, --no-whole-video keeps the modeled figure), the trained_norm_weights sub-record (--trained-evals) and the CPU
+baseline (--no-cpu-baseline, --no-cpu-config1).
 N > 1 (one rank per GPU, RCCL; under torch.distributed.run, or started by bench.py itself when launched plainly): the video's token sequence is sharded context-parallel over
 the N ranks (K/V all-gather over xGMI), the decode is banded over the ranks; all ranks work on the
 same video (strong scaling). Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement").
@@ -49,6 +54,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10, help="timed sampler evaluations")
     ap.add_argument("--warmup", type=int, default=2, help="untimed sampler evaluations before timing")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (the latent state, float32) as DIR/latents.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the plain run, also time one whole video end to end (it then gives the value), the "
+                         "trained-size norm weights sub-record and the CPU baseline")
     ap.add_argument("--num-steps", type=int, default=35, help="UniPC steps (35 = the metric)")
     ap.add_argument("--frames", type=int, default=121)
     ap.add_argument("--model", default="2B/post-trained",
@@ -67,17 +77,17 @@ def parse():
                     help="trained-size norm weights: the online max instead of the gated pair on the measured key "
                          "bound (dit.data_tight_k_bound, on by default since round 6)")
     ap.add_argument("--no-whole-video", action="store_true",
-                    help="skip the end-to-end video (value is then the per-evaluation model; for quick A/B runs)")
+                    help="--full: skip the end-to-end video (value is then the per-evaluation model, as in a plain run)")
     ap.add_argument("--no-cfg-share", action="store_true",
                     help="every CFG entry computes block 0's shared self-attention prefix (A/B of the sharing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (0: the host cores this process may use, capped by OMP_NUM_THREADS)")
     ap.add_argument("--no-cpu-config1", action="store_true",
-                    help="skip the CPU leg's end-to-end BASELINE config 1 video (~30-60 s with the weight setup; on by "
-                         "default: the whole-video CPU baseline SURVEY.md §8(d) asks for)")
+                    help="--full: skip the CPU leg's end-to-end BASELINE config 1 video (~30-60 s with the weight setup; "
+                         "the whole-video CPU baseline SURVEY.md §8(d) asks for)")
     ap.add_argument("--trained-evals", type=int, default=4,
-                    help="N = 1: after the metric run, time this many evaluations with q/k norm weights uniform in "
+                    help="--full, N = 1: after the metric run, time this many evaluations with q/k norm weights uniform in "
                          "[0.5, 3] (the attention form a trained checkpoint gets) as the line's trained_norm_weights "
                          "sub-record (0: skip)")
     ap.add_argument("--backend", default="nccl", help="process-group backend for N > 1 (nccl = RCCL; gloo only "
@@ -120,6 +130,23 @@ class _Timer:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = tt.item()
         return out, el
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump(out_dir: str, name: str, t: torch.Tensor) -> None:
+    """out_dir/name.npy, float32: the whole tensor, or (past DUMP_MAX_BYTES) a fixed seeded sample of its elements in
+    index order."""
+    flat = t.detach().float().reshape(-1)
+    keep = DUMP_MAX_BYTES // 4
+    if flat.numel() > keep:
+        idx = np.sort(np.random.RandomState(11).randint(0, flat.numel(), size=keep))
+        flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arr = flat.cpu().numpy()
+    else:
+        arr = flat.cpu().numpy().reshape(tuple(t.shape))
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def _free_port() -> int:
@@ -169,7 +196,8 @@ def main():
     from cosmos_predict2 import _native
 
     _native.load_library()
-    h, w = (int(x) for x in a.resolution.split(","))
+    torch.manual_seed(0)  # every input below has its own seeded generator; this pins whatever draws from the global one
+    h, w =(int(x) for x in a.resolution.split(","))
     state_t = 1 + (a.frames - 1) // 4
     pipe = Video2WorldInference(a.model, context_parallel_size=world, device=dev, state_t=state_t,
                                 linear_precision=a.linear_precision, attention_precision=a.attention_precision)
@@ -194,13 +222,15 @@ def main():
     state_shape = (model.config.state_ch, state_t, h // 8, w // 8)
     timer = _Timer(world, dev)
 
-    # ---- kernel-load prime (untimed): encode, one evaluation, a 2-latent-frame decode
+    # ---- kernel-load prime (untimed): encode, one evaluation, a 2-latent-frame decode. A plain run leaves the
+    # evaluation's kernels to its own warm-up evaluations (one is run here only when it has none)
     with torch.no_grad():
         gt = model.encode_conditioning(batch["video"], 1, state_t)
         run = model.begin_sampling(gt, batch["t5_text_embeddings"], batch["neg_t5_text_embeddings"],
                                    state_shape=state_shape, num_conditional_frames=1, guidance=7, seed=0,
                                    num_steps=a.num_steps)
-        run.step()
+        if a.full or a.warmup < 1:
+            run.step()
         model.decode(run.latents()[:, :, :2])
         del run, gt
 
@@ -230,8 +260,12 @@ def main():
         video, t_dec = timer(lambda: model.decode(lat))
         assert video.shape[2] == frames and torch.isfinite(video.float()).all()
         del video
+        if a.dump_outputs and rank == 0:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            _dump(a.dump_outputs, "latents", lat)
+        del lat
         t_whole = None
-        if not a.no_whole_video:
+        if a.full and not a.no_whole_video:
             def whole():
                 g0 = model.encode_conditioning(batch["video"], 1, state_t)
                 r0 = model.begin_sampling(g0, batch["t5_text_embeddings"], batch["neg_t5_text_embeddings"],
@@ -251,7 +285,7 @@ def main():
         # evaluations alternate, one each per pair, so clock drift over the run cannot bias the ratio
         kernels_metric = net.attention_kernels(state_t * (h // 16) * (w // 16))  # before the weights change below
         trained = None
-        if world == 1 and not a.norm_weights and a.trained_evals > 0:
+        if a.full and world == 1 and not a.norm_weights and a.trained_evals > 0:
             names = [k_ for k_ in net.sd if k_.endswith(("q_norm.weight", "k_norm.weight"))]
             w_unit = {k_: net.sd[k_].clone() for k_ in names}
             gw = torch.Generator(device=dev).manual_seed(7)
@@ -325,7 +359,7 @@ def main():
                      "max_attention_ms_per_eval": max(r["attention_ms_per_eval"] for r in every)}
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         sys.path.insert(0, ROOT)
         from oracle.cpu_baseline import config1_end_to_end, dit_block_sample, host_threads
 
@@ -354,6 +388,7 @@ def main():
             "value": frames / t_whole if t_whole is not None else modeled,
             "unit": "frames/s",
             "n_gpus": world,
+            "full": a.full,
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": t_step * 1e3,
