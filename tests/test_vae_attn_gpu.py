@@ -5,8 +5,11 @@ q / k / v [b*t, 1, h*w, 384] (flash / efficient backends: fp32 scores and sums, 
 vs fp32 softmax(q k^T / sqrt(384)) v of the same bf16 inputs (bf16 P + one output rounding; measured printed).
 Covers strided column slices of a [T, L, 3C] to_qkv buffer (the product's call), T > 1, ragged Lq / Lk (not a
 multiple of the 128-query block or the 32-key tile), Lk != Lq (the banded decode's gathered keys), and a
-row whose scores span a wide range: a key far above the first key tile's maximum overflows the one-pass shift,
-so its query blocks take the exact-max redo launch.
+key whose scores span a wide range (one key row scaled by 6: that key's scores have a standard deviation of about 8.7
+log2 units, so some rows put that key 2^20 and more above the first key tile's max). That covers large finite P in
+the one-pass form; whether any row crosses the 24-unit threshold of the exact-max redo launch is about a coin flip, and
+the output is finite either way, so this test does not show that the redo ran. The redo launch, its threshold and the
+split merge are pinned down by test_vae_attn_edges_gpu.py.
 """
 import pytest
 import torch
@@ -43,7 +46,7 @@ def test_vae_attn_gathered_keys_and_wide_scores(device):
     g = torch.Generator(device=device).manual_seed(3)
     q = torch.randn(1, 512, C, device=device, generator=g).to(torch.bfloat16)
     k = torch.randn(1, 1536, C, device=device, generator=g)
-    k[0, 700] *= 6.0  # one key far above the rest: scores of up to ~100 in log2 units
+    k[0, 700] *= 6.0  # one key with widely spread scores: std ~8.7 log2 units (the redo launch: see the edges file)
     k = k.to(torch.bfloat16)
     v = torch.randn(1, 1536, C, device=device, generator=g).to(torch.bfloat16)
     out = N.vae_attn(q, k, v)

@@ -86,6 +86,29 @@ def test_softmax_rows(device, rows, cols):
         N.softmax_rows(s.to(torch.bfloat16), scale)
 
 
+@pytest.mark.parametrize("sliced_out", [False, True], ids=["sliced_s", "sliced_s_and_out"])
+def test_softmax_rows_column_slices(device, sliced_out):
+    """test_softmax_rows' two assertions through softmax_rows(s, scale, out=...) on views: s a column slice
+    big[:, 1:1001] of a wider fp32 matrix (rows 4 B off a 16-B boundary: the scalar loop, vec = 0, with ld_s > cols),
+    and out a column slice of a sentinel-filled bf16 matrix whose other columns must stay untouched."""
+    rows, cols = 64, 1000
+    g = torch.Generator().manual_seed(rows + cols + 1)
+    big = (6 * torch.randn(rows, cols + 8, generator=g)).to(device)
+    s = big[:, 1:1 + cols]
+    assert s.data_ptr() % 16 == 4 and s.stride(0) > cols
+    scale = 384 ** -0.5
+    pbig = torch.full((rows, cols + 6), -1.5e30, dtype=torch.bfloat16, device=device)
+    out = pbig[:, 3:3 + cols] if sliced_out else torch.empty(rows, cols, dtype=torch.bfloat16, device=device)
+    p = N.softmax_rows(s, scale, out=out)
+    assert p.data_ptr() == out.data_ptr()
+    ref = torch.softmax(s * scale, -1)
+    assert ((p.float() - ref).abs() <= 2 ** -8 * ref + 1e-30).all()
+    assert ((p.float().sum(-1) - 1).abs() <= 4e-3).all()
+    if sliced_out:
+        guard = torch.tensor(-1.5e30, dtype=torch.bfloat16, device=device)
+        assert (pbig[:, :3] == guard).all() and (pbig[:, 3 + cols:] == guard).all()
+
+
 @pytest.fixture(scope="module")
 def vae_pair():
     sd = init_vae_state_dict(seed=0)
