@@ -69,8 +69,10 @@ __device__ __forceinline__ float hn_rope(float v, float partner, float sgn, floa
 // Branch-free, two v_rcp_f32 and one v_exp_f32 against libm erff's ~39 ops with two paths: the GEMM epilogue
 // runs it on 1.8e9 values per MLP. Within 8e-6 relative of the float64 GELU for |x| < 9; rounded to bf16 it
 // differs from the correctly rounded value on 1.4e-5 of N(0, 1.5^2) inputs (by one ulp; libm-level accuracy).
+// z is kept finite, so that x = +inf gives q = 0 or 1 and erfc = 0, hence +inf (at z = inf q was inf * 0: NaN for +inf
+// as well). No finite x reaches the bound, and -inf and NaN still give NaN (-inf * 0, as torch's GELU).
 __device__ __forceinline__ float gelu_erf(float x) {
-  const float z = fabsf(x) * 0.70710678118654752440f;
+  const float z = fminf(fabsf(x) * 0.70710678118654752440f, 3.402823466e38f);
   const float q = (z - 2.f) * __builtin_amdgcn_rcpf(z + 2.f);
   float p = -0x1.9d90e0p-12f;
   p = fmaf(p, q, -0x1.408798p-10f);
