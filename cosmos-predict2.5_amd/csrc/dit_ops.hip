@@ -20,6 +20,8 @@
 //                          (video2world_model_rectified_flow.py:131-136, :206-210)
 // Token-major layout everywhere: activations are [tokens, B, D] (batch inner), latents are kept in
 // "patch layout" [tokens, 64] with index (p1*2+p2)*16 + C, so CP shards are contiguous token ranges.
+#include <initializer_list>
+
 #include "cp25_common.h"
 
 #pragma clang fp contract(off)
@@ -113,7 +115,7 @@ __global__ void __launch_bounds__(256) ln_mod_kernel(
     for (int i = 0; i < NC * 8; ++i) amax = fmaxf(amax, fabsf(v[i]));
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) amax = fmaxf(amax, __shfl_xor(amax, m));
-    const float inv = amax > 0.f ? 448.f / amax : 0.f;
+    const float inv = 448.f / fmaxf(amax, 0x1p-100f);  // quant_fp8_rows_kernel's floor (fp8_ops.hip)
     if (lane == 0) h_scale[row] = amax / 448.f;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -410,6 +412,19 @@ __global__ void __launch_bounds__(256) cfg_velocity_kernel(const float* __restri
 
 // ============================================================================ C ABI
 namespace {
+// the kernels read and write rows in 16-byte pieces: every pointer they do that through must be 16-byte aligned
+// (nullptr passes) and every element stride a multiple of the 8 bf16 such a piece holds
+inline bool aligned16(std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= (uintptr_t)p;
+  return (bits & 15) == 0;
+}
+inline bool mult8(std::initializer_list<int64_t> strides) {
+  int64_t bits = 0;
+  for (int64_t v : strides) bits |= v;
+  return (bits & 7) == 0;
+}
+
 template <bool FP8>
 int launch_ln_mod(const void* x, int64_t x_st, int64_t x_sb, const void* y, const void* gate, const void* shift,
                   const void* scale, int64_t mod_sb, int64_t mod_st, void* x_out, void* h_out, void* h8_out,
@@ -418,6 +433,10 @@ int launch_ln_mod(const void* x, int64_t x_st, int64_t x_sb, const void* y, cons
   if (n_tok <= 0 || B <= 0 || hw <= 0 || !x || !shift || !scale) return CP25_ERR_INVAL;
   if (FP8 ? (!h8_out || !h_scale) : !h_out) return CP25_ERR_INVAL;
   if (y != nullptr && (gate == nullptr || x_out == nullptr)) return CP25_ERR_INVAL;
+  // h8 rows go out in 8-byte pieces, the row scales as single floats
+  if (!aligned16({x, y, gate, shift, scale, x_out, h_out}) || !mult8({x_st, x_sb, mod_sb, mod_st}) ||
+      ((uintptr_t)h8_out & 7) || ((uintptr_t)h_scale & 3))
+    return CP25_ERR_INVAL;
   const int64_t rows = n_tok * B;
   const dim3 grid((unsigned)cdiv(rows, 4));
   auto* X = (const unsigned short*)x;
@@ -464,6 +483,9 @@ extern "C" int cp25_final_ln_mod(const void* x, const void* y, const void* gate,
                                  int64_t n_tok, int B, int D, int64_t tok0, int64_t hw, float eps, hipStream_t stream) {
   if (n_tok <= 0 || B <= 0 || hw <= 0 || !x || !shift || !scale || !out) return CP25_ERR_INVAL;
   if (y != nullptr && gate == nullptr) return CP25_ERR_INVAL;
+  // shift and scale are read one float at a time
+  if (!aligned16({x, y, gate, out}) || !mult8({gmod_sb, gmod_st}) || (((uintptr_t)shift | (uintptr_t)scale) & 3))
+    return CP25_ERR_INVAL;
   const int64_t rows = n_tok * B;
   const dim3 grid((unsigned)cdiv(rows, 4));
   auto* X = (const unsigned short*)x;
@@ -529,6 +551,9 @@ extern "C" int cp25_head_rmsnorm_rope_nmax(void* buf, int64_t row_stride, int64_
   if (!buf || !weight || n_rows <= 0 || H <= 0 || B <= 0) return CP25_ERR_INVAL;
   if ((row_stride % 8) || (head_off % 8) || ((cos_tab == nullptr) != (sin_tab == nullptr))) return CP25_ERR_INVAL;
   if ((uintptr_t)norm_max_slots & 3) return CP25_ERR_INVAL;
+  if (!aligned16({buf, weight, out2}) || (out2 != nullptr && (out2_stride % 8)) ||
+      (((uintptr_t)cos_tab | (uintptr_t)sin_tab) & 3))
+    return CP25_ERR_INVAL;
   const int64_t items = n_rows * H;
   if (norm_max_slots)
     hipLaunchKernelGGL(head_rmsnorm_rope_kernel<true>, dim3((unsigned)cdiv(items, 16)), dim3(256), 0, stream,
@@ -544,7 +569,8 @@ extern "C" int cp25_head_rmsnorm_rope_nmax(void* buf, int64_t row_stride, int64_
 
 extern "C" int cp25_copy_rows(const void* src, int64_t src_stride, void* dst, int64_t dst_stride, int64_t n_rows,
                               int64_t width, hipStream_t stream) {
-  if (!src || !dst || n_rows <= 0 || width <= 0 || (width % 8) || (src_stride % 8) || (dst_stride % 8))
+  if (!src || !dst || n_rows <= 0 || width <= 0 || (width % 8) || (src_stride % 8) || (dst_stride % 8) ||
+      !aligned16({src, dst}))
     return CP25_ERR_INVAL;
   const int64_t n = n_rows * (width / 8);
   hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, stream,
@@ -554,7 +580,7 @@ extern "C" int cp25_copy_rows(const void* src, int64_t src_stride, void* dst, in
 }
 
 extern "C" int cp25_gelu(void* x, int64_t n, hipStream_t stream) {
-  if (!x || n <= 0 || (n % 8)) return CP25_ERR_INVAL;
+  if (!x || n <= 0 || (n % 8) || !aligned16({x})) return CP25_ERR_INVAL;
   const int64_t n8 = n / 8;
   hipLaunchKernelGGL(gelu_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, stream, (unsigned short*)x, n8);
   CP25_LAUNCH_CHECK();

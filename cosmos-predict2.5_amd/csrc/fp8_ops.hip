@@ -3,7 +3,8 @@
 // torch._scaled_mm with a per-row activation scale and a per-output-channel weight scale; these
 // kernels produce the row-scaled activation operand.
 //
-//   cp25_quant_fp8_rows : x bf16 [M, K] -> q fp8 [M, K], s fp32 [M], x[m, k] ~= q[m, k] * s[m]
+//   cp25_quant_fp8_rows : x bf16 [M, K] -> q fp8 [M, K], s fp32 [M], x[m, k] ~= q[m, k] * s[m]:
+//                         s = max|row| / 448, q = e4m3(x * (448 / max(max|row|, 2^-100)))
 //   cp25_gelu_quant_fp8 : the same over GELU(x) (minimal_v4_dit.py:249-254; a 7.1.26-erfc GELU within
 //                         ~1 bf16 ulp of the exact one, rounded to bf16 first), so the MLP's hidden
 //                         activation is read once and never written back in bf16
@@ -19,6 +20,7 @@
 namespace {
 
 constexpr float kFp8Max = 448.f;  // largest finite OCP E4M3 value
+constexpr float kAmaxFloor = 0x1p-100f;  // rows (heads) below it are quantised as if this were their largest magnitude
 
 // GELU for the fp8 operand: x * Phi(x) with Phi from the Abramowitz-Stegun 7.1.26 erfc form
 // erfc(z) = t (a1 + t (a2 + ...)) exp(-z^2), t = 1 / (1 + p z) (|error| <= 1.5e-7): ~14 VALU ops
@@ -82,7 +84,9 @@ __global__ void __launch_bounds__(NW * 64) quant_fp8_rows_kernel(const unsigned 
     for (int j = 0; j < WPR; ++j) amax = fmaxf(amax, red[w0 + j]);
   }
   if (!live) return;
-  const float inv = amax > 0.f ? kFp8Max / amax : 0.f;
+  // the divisor has v_cast_t_kernel's floor: 448 / amax is infinite below 448 / FLT_MAX = 1.3e-36, and 0 * inf = NaN
+  // went through the clamp as -448 for every zero of such a row. An all-zero row still gives codes 0 (0 * finite)
+  const float inv = kFp8Max / fmaxf(amax, kAmaxFloor);
   if (lane == 0 && wr == 0) s[row] = amax / kFp8Max;
   unsigned char* qr = q + base;
 #pragma unroll
@@ -215,7 +219,7 @@ __global__ void __launch_bounds__(256) v_cast_t_kernel(const unsigned short* __r
     *reinterpret_cast<u32x4*>(t + key * RS + d0) = w;
   }
   __syncthreads();
-  const float inv = 448.f / fmaxf(__uint_as_float(amax[bh]), 0x1p-100f);
+  const float inv = kFp8Max / fmaxf(__uint_as_float(amax[bh]), kAmaxFloor);
   unsigned char* out = v8t + ((int64_t)bh * ntile + tile) * 8192;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {  // 512 output chunks of 16 B: d = c / 4, p0 = 16 (c % 4)

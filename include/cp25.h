@@ -214,6 +214,8 @@ int cp25_attn_cross_select(int form);
 /* ---------------------------------------------------------------- DiT block elementwise
  * Activations are token-major [n_tok, B, D] bf16 (batch inner). Row (tok, b) uses modulation row
  * (b, t) with t = (tok0 + tok) / hw (frame index; tok0 = first global token of this CP shard).
+ * The kernels of this section move rows in 16-byte pieces: every bf16 pointer (and cp25_final_ln_mod's out) must be
+ * 16-B aligned and every bf16 element stride a multiple of 8, or the call returns CP25_ERR_INVAL before any launch.
  *
  * cp25_ln_mod: if y != NULL first x' = x + gate * y (two bf16 roundings, stored to x_out [n_tok,B,D]);
  * then h_out = LayerNorm(x', no affine, eps) * (1 + scale) + shift with the reference's bf16
@@ -274,11 +276,12 @@ int cp25_head_rmsnorm_rope_nmax(void* buf, int64_t row_stride, int64_t n_rows, i
                                 int64_t out2_stride, float eps, float out_scale, float* norm_max_slots,
                                 hipStream_t stream);
 
-/* dst[r, 0:width] = src[r, 0:width] for bf16 rows (K/V export before the CP all-gather). */
+/* dst[r, 0:width] = src[r, 0:width] for bf16 rows (K/V export before the CP all-gather); width and both strides
+ * multiples of 8, src and dst 16-B aligned. */
 int cp25_copy_rows(const void* src, int64_t src_stride, void* dst, int64_t dst_stride, int64_t n_rows, int64_t width,
                    hipStream_t stream);
 
-/* In-place exact (erf) GELU on n bf16 values (n % 8 == 0).
+/* In-place exact (erf) GELU on n bf16 values (n % 8 == 0, x 16-B aligned).
  * Replaces: GPT2FeedForward activation, minimal_v4_dit.py:249-254. */
 int cp25_gelu(void* x, int64_t n, hipStream_t stream);
 
@@ -463,8 +466,9 @@ int cp25_softmax_rows(const float* s, int64_t rows, int cols, int64_t ld_s, floa
 
 /* fp8 activation operand of the DiT's fp8 linear layers (config 5's "fp8 MFMA"; the GEMM is cp25_gemm_fp8 /
  * cp25_gemm_fp8_res, hand-written; torch._scaled_mm is only the tests' reference). Per row m of x [n_rows, k] bf16 (contiguous, k in {512, 1024, 1536,
- * 2048, 3072, 4096, 5120, 6144, 8192, 20480}): scale[m] = max|x[m, :]| / 448 and q[m, :] = fp8_e4m3(x[m, :] * 448 / max|x[m, :]|)
- * (OCP E4M3, round to nearest even, saturated), so x ~= q * scale; an all-zero row gives q = 0, scale 0.
+ * 2048, 3072, 4096, 5120, 6144, 8192, 20480}): scale[m] = max|x[m, :]| / 448 and q[m, :] = fp8_e4m3(x[m, :] * (448 / max(max|x[m, :]|, 2^-100)))
+ * (OCP E4M3, round to nearest even, saturated), so x ~= q * scale; an all-zero row gives q = 0, scale 0, and a row below
+ * the 2^-100 floor (where 448 / max would overflow) gives q = 0 with its tiny scale.
  * cp25_gelu_quant_fp8 quantises GELU(x) rounded to bf16 (Abramowitz-Stegun 7.1.26 erfc: within ~1 bf16 ulp
  * of cp25_gelu's exact-erf value, far below the fp8 rounding).
  * Replaces: the bf16 operand of nn.Linear in Attention (minimal_v4_dit.py:400-432) and GPT2FeedForward
