@@ -124,6 +124,10 @@ SIGNATURES = {
     "cp25_attn_fwd_t": [_T, _T, _T, _T, _F, _P, ctypes.c_size_t, _P],
     "cp25_gemm_epi_t": [_T, _T, _T, _I, _P],
     "cp25_conv3d_t": [_T, _I, _T, _T, _T, _I, _I, _I, _I, _I, _I, _P],
+    "cp25_resize_crop_u8": [_P, c_int64_p, _I, _I, _I, _I, _P, c_int64_p, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I,
+                            _I, _I, _I, _P],
+    "cp25_u8_to_clip": [_P, c_int64_p, _I, _I, _I, _I, _P, _P],
+    "cp25_clip_to_u8": [_P, c_int64_p, _I, _I, _I, _I, _P, c_int64_p, _P],
 }
 
 
@@ -913,4 +917,92 @@ def softmax_rows(s: torch.Tensor, scale: float, out: Optional[torch.Tensor] = No
     rc = lib.cp25_softmax_rows(_ptr(s), rows, cols, s.stride(0), float(scale), _ptr(out), out.stride(0),
                                _stream(s.device))
     _check("cp25_softmax_rows", rc)
+    return out
+
+
+# ----------------------------------------------------------------------------- pixels
+RESIZE_MAX_RATIO = 4  # cp25_resize_crop_u8: in / out per axis
+RESIZE_MAX_TAPS = 9
+
+
+def _i64x4(vals) -> ctypes.Array:
+    return (ctypes.c_int64 * 4)(*[int(v) for v in vals])
+
+
+def _check_table(name: str, table, n_out: int, device) -> int:
+    start, count, w = table
+    if (start.dtype != torch.int32 or count.dtype != torch.int32 or w.dtype != torch.float32 or w.dim() != 2
+            or start.shape != (n_out,) or count.shape != (n_out,) or w.shape[0] != n_out
+            or not (start.is_contiguous() and count.is_contiguous() and w.is_contiguous())
+            or not (start.device == count.device == w.device == device)):
+        raise ValueError(f"resize_crop_u8: {name} tables must be contiguous int32 start[{n_out}], int32 count[{n_out}] "
+                         f"and fp32 w[{n_out}][taps] on the source's device")
+    if not 1 <= w.shape[1] <= RESIZE_MAX_TAPS:
+        raise ValueError(f"resize_crop_u8: {name} table has {w.shape[1]} taps; the kernel holds at most "
+                         f"{RESIZE_MAX_TAPS} (in / out <= {RESIZE_MAX_RATIO})")
+    return w.shape[1]
+
+
+def resize_crop_u8(src: torch.Tensor, dst: torch.Tensor, y_table, x_table, window) -> torch.Tensor:
+    """cp25_resize_crop_u8: src uint8 [N, C, Hin, Win] (any strides, e.g. a permuted [N, H, W, C] tensor) ->
+    dst uint8 [N, C, th, tw] (any strides), the (top, left, th, tw) = `window` part of the antialiased resize to
+    (rh, rw) = (len(y_table start), len(x_table start)). A table is (start int32 [out], count int32 [out],
+    w fp32 [out, taps]) on the device (pixels.aa_tables_device)."""
+    lib = load_library()
+    for n, t in (("src", src), ("dst", dst)):
+        if t.dtype != torch.uint8 or t.dim() != 4:
+            raise ValueError(f"resize_crop_u8: {n} must be a 4-D uint8 tensor [N, C, H, W], got {t.dtype} {tuple(t.shape)}")
+    N, C, Hin, Win = src.shape
+    top, left, th, tw = (int(v) for v in window)
+    rh, rw = y_table[0].shape[0], x_table[0].shape[0]
+    if C > 4:
+        raise ValueError(f"resize_crop_u8: {C} channels; the kernel handles at most 4")
+    if Hin > RESIZE_MAX_RATIO * rh or Win > RESIZE_MAX_RATIO * rw:
+        raise ValueError(f"resize_crop_u8: ({Hin}, {Win}) -> ({rh}, {rw}) shrinks by more than {RESIZE_MAX_RATIO} "
+                         "on an axis (the kernel's tap limit)")
+    if dst.shape != (N, C, th, tw) or dst.device != src.device:
+        raise ValueError(f"resize_crop_u8: dst must be [{N}, {C}, {th}, {tw}] on the source's device")
+    if top < 0 or left < 0 or th < 1 or tw < 1 or top + th > rh or left + tw > rw:
+        raise ValueError(f"resize_crop_u8: window {tuple(window)} leaves the resized extent ({rh}, {rw})")
+    yt = _check_table("y", y_table, rh, src.device)
+    xt = _check_table("x", x_table, rw, src.device)
+    rc = lib.cp25_resize_crop_u8(_ptr(src), _i64x4(src.stride()), N, C, Hin, Win, _ptr(dst), _i64x4(dst.stride()),
+                                 _ptr(y_table[0]), _ptr(y_table[1]), _ptr(y_table[2]), yt, _ptr(x_table[0]),
+                                 _ptr(x_table[1]), _ptr(x_table[2]), xt, rh, rw, top, left, th, tw, _stream(src.device))
+    _check("cp25_resize_crop_u8", rc)
+    return dst
+
+
+def u8_to_clip(video: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cp25_u8_to_clip: uint8 [C, T, H, W] (any strides, C <= 16) -> the encoder's clip [T, H, W, 16] bf16:
+    u / 127.5 - 1 in bf16 arithmetic in channels < C, zeros above."""
+    lib = load_library()
+    if video.dtype != torch.uint8 or video.dim() != 4:
+        raise ValueError(f"u8_to_clip: video must be a 4-D uint8 tensor [C, T, H, W], got {video.dtype} {tuple(video.shape)}")
+    C, T, H, W = video.shape
+    if C > 16:
+        raise ValueError(f"u8_to_clip: {C} channels; the clip has 16")
+    if out is None:
+        out = torch.empty((T, H, W, 16), dtype=torch.bfloat16, device=video.device)
+    if out.shape != (T, H, W, 16) or out.dtype != torch.bfloat16 or not out.is_contiguous() or out.device != video.device:
+        raise ValueError(f"u8_to_clip: out must be a contiguous bf16 [{T}, {H}, {W}, 16] tensor on the video's device")
+    rc = lib.cp25_u8_to_clip(_ptr(video), _i64x4(video.stride()), C, T, H, W, _ptr(out), _stream(video.device))
+    _check("cp25_u8_to_clip", rc)
+    return out
+
+
+def clip_to_u8(clip: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """cp25_clip_to_u8: bf16 [T, H, W, C] (any strides, C <= 4) -> uint8 `out` [T, H, W, C] (any strides, e.g. a
+    permuted view of a [1, C, T, H, W] tensor): trunc(clamp((v + 1) / 2, 0, 1) * 255)."""
+    lib = load_library()
+    if clip.dtype != torch.bfloat16 or clip.dim() != 4:
+        raise ValueError(f"clip_to_u8: clip must be a 4-D bf16 tensor [T, H, W, C], got {clip.dtype} {tuple(clip.shape)}")
+    T, H, W, C = clip.shape
+    if C > 4:
+        raise ValueError(f"clip_to_u8: {C} channels; the kernel handles at most 4")
+    if out.dtype != torch.uint8 or out.shape != clip.shape or out.device != clip.device:
+        raise ValueError(f"clip_to_u8: out must be a uint8 [{T}, {H}, {W}, {C}] tensor on the clip's device")
+    rc = lib.cp25_clip_to_u8(_ptr(clip), _i64x4(clip.stride()), T, H, W, C, _ptr(out), _i64x4(out.stride()),
+                             _stream(clip.device))
+    _check("cp25_clip_to_u8", rc)
     return out

@@ -136,6 +136,9 @@ class ActionConditionedInference:
         img = initial_frame
         chunks = []
         total = 0
+        on_device = getattr(self.pipe, "pixel_path", "host") == "device"
+        if on_device:  # the running frame lives on the GPU as uint8 [3, H, W]
+            img = torch.from_numpy(np.ascontiguousarray(initial_frame)).to(self.pipe.device).permute(2, 0, 1)
         for i in range(start_frame_idx, len(actions), chunk_size):
             a = actions[i:i + chunk_size]
             if a.shape[0] != chunk_size:  # zero-pad an incomplete last chunk
@@ -143,13 +146,26 @@ class ActionConditionedInference:
             n_frames = chunk_size + 1
             # the reference's to_tensor (/ 255) -> zero frames -> * 255 -> uint8 round trip is the identity on every
             # uint8 value in fp32 (tests/test_action_cpu.py), so the uint8 frame goes in as it is: [1, C, T, H, W]
-            vid = conditioning_video(img, n_frames)
-            video = self.pipe.generate_vid2world(prompt, vid, guidance=guidance, num_video_frames=n_frames,
-                                                 num_latent_conditional_frames=num_latent_conditional_frames,
-                                                 resolution=f"{H},{W}", seed=i, negative_prompt=negative_prompt,
-                                                 num_steps=num_steps, action=torch.from_numpy(a).float())
-            v = ((torch.clamp((video + 1) / 2, 0, 1)[0] * 255).to(torch.uint8).permute(1, 2, 3, 0).cpu().numpy())
-            img = v[-1]
+            if on_device:
+                # conditioning video built on the GPU from the previous chunk's last uint8 frame; decode_u8 quantises
+                # on the GPU and only the finished chunk's [T, H, W, 3] bytes cross to the host
+                vid = torch.zeros(1, 3, n_frames, H, W, dtype=torch.uint8, device=self.pipe.device)
+                vid[0, :, 0] = img
+                v8 = self.pipe.generate_vid2world(prompt, vid, guidance=guidance, num_video_frames=n_frames,
+                                                  num_latent_conditional_frames=num_latent_conditional_frames,
+                                                  resolution=f"{H},{W}", seed=i, negative_prompt=negative_prompt,
+                                                  num_steps=num_steps, action=torch.from_numpy(a).float(),
+                                                  return_uint8=True, uint8_layout="THWC")
+                img = v8[-1].permute(2, 0, 1)
+                v = v8.cpu().numpy()
+            else:
+                vid = conditioning_video(img, n_frames)
+                video = self.pipe.generate_vid2world(prompt, vid, guidance=guidance, num_video_frames=n_frames,
+                                                     num_latent_conditional_frames=num_latent_conditional_frames,
+                                                     resolution=f"{H},{W}", seed=i, negative_prompt=negative_prompt,
+                                                     num_steps=num_steps, action=torch.from_numpy(a).float())
+                v = ((torch.clamp((video + 1) / 2, 0, 1)[0] * 255).to(torch.uint8).permute(1, 2, 3, 0).cpu().numpy())
+                img = v[-1]
             chunks.append(v if not chunks else v[:chunk_size])
             total += len(chunks[-1])
             if single_chunk or (max_frames is not None and total >= max_frames):

@@ -69,6 +69,9 @@ class SetupArguments(pydantic.BaseModel):
     keep_going: bool = True
     profile: bool = False
     state_t: Optional[int] = None  # latent frames; the reference's experiments use 24 (93 frames)
+    # build-specific, like state_t (the reference has no such field): "host" resizes, normalises and quantises pixels
+    # with torch on the CPU / in fp32; "device" keeps them uint8 on the GPU (cosmos_predict2/pixels.py)
+    pixel_path: Literal["host", "device"] = "host"
 
     @pydantic.model_validator(mode="before")
     @classmethod

@@ -35,7 +35,8 @@ class Inference:
         self.rank0 = is_rank0()
         self.pipe = Video2WorldInference(args.model, ckpt_path=args.checkpoint_path, tokenizer_path=args.tokenizer_path,
                                          context_parallel_size=args.context_parallel_size or 1,
-                                         state_t=args.state_t, text_encoder=text_encoder)
+                                         state_t=args.state_t, text_encoder=text_encoder,
+                                         pixel_path=args.pixel_path)
         if self.rank0:
             Path(args.output_dir).mkdir(parents=True, exist_ok=True)
 
@@ -52,6 +53,8 @@ class Inference:
         if self.rank0:
             output_dir.mkdir(parents=True, exist_ok=True)
             (Path(str(stem) + ".json")).write_text(sample.model_dump_json())
+        # device pixel path: the pipeline returns uint8 [1, 3, T, H, W] on the GPU (decode_u8), written as it is
+        extra = {"return_uint8": True} if self.pipe.pixel_path == "device" else {}
         try:
             if sample.enable_autoregressive:
                 video = self.pipe.generate_autoregressive_from_batch(
@@ -59,18 +62,21 @@ class Inference:
                     num_output_frames=sample.num_output_frames, chunk_size=sample.chunk_size,
                     chunk_overlap=sample.chunk_overlap, guidance=sample.guidance,
                     num_latent_conditional_frames=sample.num_input_frames, resolution=sample.resolution,
-                    seed=sample.seed, negative_prompt=sample.negative_prompt, num_steps=sample.num_steps)
+                    seed=sample.seed, negative_prompt=sample.negative_prompt, num_steps=sample.num_steps, **extra)
             else:
                 video = self.pipe.generate_vid2world(
                     prompt=sample.prompt, input_path=path_to_str(sample.input_path), guidance=sample.guidance,
                     num_video_frames=sample.num_output_frames, num_latent_conditional_frames=sample.num_input_frames,
                     resolution=sample.resolution, seed=sample.seed, negative_prompt=sample.negative_prompt,
-                    num_steps=sample.num_steps)
+                    num_steps=sample.num_steps, **extra)
         except Exception:
             if self.setup_args.keep_going:
                 log.exception("sample %s failed", sample.name)
                 return None
             raise
         if self.rank0:
+            if video.dtype == torch.uint8:
+                frames = video[0].permute(1, 2, 3, 0).contiguous().cpu().numpy()
+                return write_mp4(frames, str(stem) + ".mp4", fps=16)
             return save_video((1.0 + video[0]) / 2, str(stem))
         return str(stem) + ".mp4"

@@ -60,6 +60,8 @@ class Video2WorldModelRectifiedFlow:
         # replay each trajectory's DiT forward from a HIP graph after its first evaluation (SamplingRun; one GPU only):
         # for launch-bound shapes (config 5's 13-frame chunks), where the host's launch rate leaves the device idle
         self.hip_graph = False
+        # "device": uint8 conditioning frames go through tokenizer.encode_u8 (Video2WorldInference(pixel_path=...))
+        self.pixel_path = "host"
 
     # ------------------------------------------------------------------ plumbing
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
@@ -179,8 +181,11 @@ class Video2WorldModelRectifiedFlow:
         only those frames reach the output (mask-selected in denoise, video2world_model_rectified_flow.py
         :105-107 and :131-136). The remaining latent frames are zero-filled and never read."""
         px = 1 + 4 * (n_cond - 1)
-        vid = self._normalize_video(video[:, :, :px])
-        lat = self.encode(vid).float()
+        if self.pixel_path == "device" and video.dtype == torch.uint8:
+            # uint8 straight into the encoder's clip (cp25_u8_to_clip): _normalize_video's arithmetic, no bf16 video
+            lat = self.tokenizer.encode_u8(video[:, :, :px].to(self.device)).float()
+        else:
+            lat = self.encode(self._normalize_video(video[:, :, :px])).float()
         B, C, Tc, H, W = lat.shape
         gt = torch.zeros((B, C, T_lat, H, W), dtype=torch.float32, device=self.device)
         gt[:, :, :Tc] = lat

@@ -103,14 +103,22 @@ def process_video_frames(frames_uint8_T_H_W_C: torch.Tensor, resolution, num_vid
 class Video2WorldInference:
     """Pipeline object of the reference's Video2WorldInference, on the MI355X model."""
 
+    pixel_path = "host"  # "device": uint8 pixels stay on the GPU (the constructor's keyword)
+
     def __init__(self, model_name: str = "2B/post-trained", ckpt_path: Optional[str] = None,
                  tokenizer_path: Optional[str] = None, context_parallel_size: int = 1, device=None,
                  state_t: Optional[int] = None, text_encoder: Optional[Callable] = None,
                  net_cfg: Optional[DiTConfig] = None, sampler_cfg: Optional[SamplerConfig] = None,
-                 weights_seed: int = 0, linear_precision: str = "bf16", attention_precision: str = "bf16"):
+                 weights_seed: int = 0, linear_precision: str = "bf16", attention_precision: str = "bf16",
+                 pixel_path: str = "host"):
         """linear_precision: "bf16" (the reference's arithmetic) or "fp8" (the DiT block GEMMs as fp8
         MFMA, config 5's option; MinimalV1LVGDiT.set_linear_precision). attention_precision: "bf16", "fp8qk"
-        (self-attention Q K^T on e4m3) or "fp8" (also P.V; MinimalV1LVGDiT.set_attention_precision)."""
+        (self-attention Q K^T on e4m3) or "fp8" (also P.V; MinimalV1LVGDiT.set_attention_precision).
+        pixel_path: "host" (resize, normalisation and output quantisation as torch ops, on the CPU / in fp32) or
+        "device" (uint8 pixels stay on the GPU: cosmos_predict2/pixels.py; enables return_uint8=True)."""
+        if pixel_path not in ("host", "device"):
+            raise ValueError(f"pixel_path must be 'host' or 'device', got {pixel_path!r}")
+        self.pixel_path = pixel_path
         if device is None:
             device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
         self.device = torch.device(device)
@@ -141,6 +149,7 @@ class Video2WorldInference:
             sd = init_state_dict(ncfg, seed=weights_seed, device=self.device)
         self.model.load_state_dict(sd)
         del sd
+        self.model.pixel_path = pixel_path
         self.model.net.set_linear_precision(linear_precision)
         self.model.net.set_attention_precision(attention_precision)
         if self.process_group is not None:
@@ -187,9 +196,15 @@ class Video2WorldInference:
     def generate_vid2world(self, prompt: str, input_path=None, guidance: int = 7, num_video_frames: int = 77,
                            num_latent_conditional_frames: int = 1, resolution: str = "192,320", seed: int = 1,
                            negative_prompt: str = DEFAULT_NEGATIVE_PROMPT, num_steps: int = 35,
-                           action: Optional[torch.Tensor] = None, **unused) -> torch.Tensor:
+                           action: Optional[torch.Tensor] = None, return_uint8: bool = False,
+                           uint8_layout: str = "NCTHW", **unused) -> torch.Tensor:
         """-> video [1, 3, T, H, W] in [-1, 1] (fp32). T = tokenizer.get_pixel_num_frames(state_t) (F5).
-        action: [A, action_dim] for the action-conditioned model (video2world.py:325-352)."""
+        action: [A, action_dim] for the action-conditioned model (video2world.py:325-352).
+        return_uint8 (pixel_path="device" only): -> the uint8 video on the GPU, quantised by decode_u8, as
+        [1, 3, T, H, W] (uint8_layout "NCTHW") or [T, H, W, 3] ("THWC"); no fp32 video is made."""
+        if return_uint8 and self.pixel_path != "device":
+            raise ValueError("return_uint8=True needs Video2WorldInference(pixel_path='device')")
+        dev_px = self.pixel_path == "device"
         if resolution == "none":
             h, w = VIDEO_RES_SIZE_INFO[self.model.config.resolution]["9,16"]
         else:
@@ -201,12 +216,19 @@ class Video2WorldInference:
         elif isinstance(input_path, str):
             ext = os.path.splitext(input_path)[1].lower()
             if ext in _IMAGE_EXTENSIONS:
-                vid = read_and_process_image(input_path, (h, w), frames)
+                vid = (self._image_video_device(input_path, (h, w), frames) if dev_px
+                       else read_and_process_image(input_path, (h, w), frames))
             elif ext in _VIDEO_EXTENSIONS:  # read_and_process_video (video2world.py:150-233)
                 from .video_io import read_mp4
 
-                vid = process_video_frames(torch.from_numpy(read_mp4(input_path)), (h, w), frames,
-                                           num_latent_conditional_frames)
+                if dev_px:
+                    from .pixels import process_video_frames_device
+
+                    vid = process_video_frames_device(torch.from_numpy(read_mp4(input_path)), (h, w), frames,
+                                                      num_latent_conditional_frames, device=self.device)
+                else:
+                    vid = process_video_frames(torch.from_numpy(read_mp4(input_path)), (h, w), frames,
+                                               num_latent_conditional_frames)
             else:
                 raise ValueError(f"Unsupported file extension: {ext}")
         elif isinstance(input_path, torch.Tensor):
@@ -222,7 +244,10 @@ class Video2WorldInference:
                                                          num_steps=num_steps)
         torch.cuda.synchronize(self.device)
         t1 = time.perf_counter()
-        video = self.model.decode(latents).float()
+        if return_uint8:
+            video = self.model.tokenizer.decode_u8(latents, uint8_layout)
+        else:
+            video = self.model.decode(latents).float()
         torch.cuda.synchronize(self.device)
         self.last_timing = {"encode_and_sample_s": t1 - t0, "decode_s": time.perf_counter() - t1}
         return video
@@ -232,7 +257,8 @@ class Video2WorldInference:
                                            chunk_overlap: int, guidance: int = 7,
                                            num_latent_conditional_frames: int = 1, resolution: str = "192,320",
                                            seed: int = 1, negative_prompt: str = DEFAULT_NEGATIVE_PROMPT,
-                                           num_steps: int = 35, **unused) -> torch.Tensor:
+                                           num_steps: int = 35, return_uint8: bool = False,
+                                           **unused) -> torch.Tensor:
         """Sliding-window long-video generation (video2world.py:582-810), byte-for-byte the reference's
         window: a running uint8 input video `current_input_video` of num_output_frames frames; chunk i
         covers frames [i*(chunk_size-overlap), +chunk_size) (zero-padded to the model's frame count),
@@ -240,13 +266,23 @@ class Video2WorldInference:
         reference passes the pixel overlap there, :761-765), and writes its frames from
         [start + cond, end) back into the running video, re-quantised by truncation
         ((v/2 + 0.5).clamp(0, 1) * 255).to(uint8) (:796-804). Output: chunk 0 whole, later chunks
-        without their first `chunk_overlap` frames (:785-793)."""
+        without their first `chunk_overlap` frames (:785-793).
+        Under pixel_path="device" the running video stays on the GPU and each chunk is written back from the
+        decoder's uint8 result (cp25_clip_to_u8, the same truncation), so the loop makes no fp32 video and no host
+        copy; return_uint8=True then returns the uint8 pieces concatenated instead of the fp32 ones."""
+        dev_px = self.pixel_path == "device"
+        if return_uint8 != dev_px:
+            raise ValueError("the autoregressive loop returns uint8 video under pixel_path='device' (pass "
+                             "return_uint8=True) and fp32 video under pixel_path='host'")
         if resolution == "none":
             h, w = VIDEO_RES_SIZE_INFO[self.model.config.resolution]["9,16"]
         else:
             h, w = (int(x) for x in resolution.split(","))
         frames = self.model.tokenizer.get_pixel_num_frames(self.model.config.state_t)
-        full = self._ar_input_video(input_path, num_output_frames, num_latent_conditional_frames, (h, w))
+        if dev_px:
+            full = self._ar_input_video_device(input_path, num_output_frames, num_latent_conditional_frames, (h, w))
+        else:
+            full = self._ar_input_video(input_path, num_output_frames, num_latent_conditional_frames, (h, w))
         step = chunk_size - chunk_overlap
         if step <= 0:
             raise ValueError(f"chunk_overlap {chunk_overlap} must be smaller than chunk_size {chunk_size}")
@@ -262,9 +298,17 @@ class Video2WorldInference:
             n = end - start
             chunk_in = current[:, :, start:end]
             if n < frames:
-                pad = torch.zeros(chunk_in.shape[:2] + (frames - n,) + chunk_in.shape[3:], dtype=chunk_in.dtype)
+                pad = torch.zeros(chunk_in.shape[:2] + (frames - n,) + chunk_in.shape[3:], dtype=chunk_in.dtype,
+                                  device=chunk_in.device)
                 chunk_in = torch.cat([chunk_in, pad], dim=2)
             n_cond = num_latent_conditional_frames if ci == 0 else chunk_overlap
+            if dev_px:
+                v8 = self.generate_vid2world(prompt, chunk_in, guidance, frames, n_cond, resolution, seed + ci,
+                                             negative_prompt, num_steps, return_uint8=True)[:, :, :n]
+                pieces.append(v8 if ci == 0 else v8[:, :, chunk_overlap:])
+                if ci < n_chunks - 1:
+                    current[:, :, start + n_cond:end] = v8[:, :, n_cond:]
+                continue
             video = self.generate_vid2world(prompt, chunk_in, guidance, frames, n_cond, resolution, seed + ci,
                                             negative_prompt, num_steps)
             video = video[:, :, :n]
@@ -273,6 +317,48 @@ class Video2WorldInference:
                 v8 = ((video / 2.0 + 0.5).clamp(0.0, 1.0) * 255.0).to(torch.uint8)
                 current[:, :, start + n_cond:end] = v8[:, :, n_cond:].to(current.device)
         return torch.cat(pieces, dim=2)
+
+    def _image_video_device(self, img_path: str, resolution, num_frames: int) -> torch.Tensor:
+        """read_and_process_image / the AR loop's image branch on the device: the decoded image is uploaded as
+        uint8 [1, H, W, 3], resized by cp25_resize_crop_u8 into frame 0 of a zero uint8 [1, 3, num_frames, h, w]."""
+        from .pixels import resize_input_device
+
+        ext = os.path.splitext(img_path)[1]
+        if ext.lower() not in _IMAGE_EXTENSIONS:
+            raise ValueError(f"Invalid image extension: {ext}")
+        from PIL import Image
+
+        img = torch.from_numpy(np.asarray(Image.open(img_path).convert("RGB")).copy())[None].to(self.device)
+        h, w = resolution
+        vid = torch.zeros(1, 3, num_frames, h, w, dtype=torch.uint8, device=self.device)
+        vid[0, :, 0] = resize_input_device(img, (h, w), layout="THWC")[0].permute(2, 0, 1)
+        return vid
+
+    def _ar_input_video_device(self, input_path, num_output_frames: int, num_latent_conditional_frames: int,
+                               resolution) -> torch.Tensor:
+        """_ar_input_video with the video on the GPU (image and mp4 inputs resized there)."""
+        h, w = resolution
+        if input_path is None or num_latent_conditional_frames == 0:
+            return torch.zeros(1, 3, num_output_frames, h, w, dtype=torch.uint8, device=self.device)
+        if isinstance(input_path, torch.Tensor):
+            v = input_path.to(self.device)
+            if v.shape[2] < num_output_frames:
+                pad = torch.zeros(v.shape[:2] + (num_output_frames - v.shape[2],) + v.shape[3:], dtype=v.dtype,
+                                  device=v.device)
+                v = torch.cat([v, pad], dim=2)
+            return v
+        if not isinstance(input_path, str):
+            raise ValueError(f"Unsupported input_path type: {type(input_path)}")
+        ext = os.path.splitext(input_path)[1].lower()
+        if ext in _IMAGE_EXTENSIONS:
+            return self._image_video_device(input_path, resolution, num_output_frames)
+        if ext in _VIDEO_EXTENSIONS:
+            from .pixels import process_video_frames_device
+            from .video_io import read_mp4
+
+            return process_video_frames_device(torch.from_numpy(read_mp4(input_path)), resolution, num_output_frames,
+                                               num_latent_conditional_frames, validate=False, device=self.device)
+        raise ValueError(f"Unsupported file extension: {ext}")
 
     @staticmethod
     def _ar_input_video(input_path, num_output_frames: int, num_latent_conditional_frames: int,

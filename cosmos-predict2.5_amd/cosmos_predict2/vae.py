@@ -391,6 +391,20 @@ class WanVAE:
         _, C, T, H, W = video.shape
         x = torch.zeros((T, H, W, 16), dtype=BF16, device=self.device)  # channels padded 3 -> 16
         x[..., :C] = video[0].to(self.device, BF16).permute(1, 2, 3, 0)
+        return self._encode_clip(x)
+
+    @torch.no_grad()
+    def encode_u8(self, video_u8: torch.Tensor) -> torch.Tensor:
+        """uint8 device video [1, 3, T, H, W] (any strides) -> mu, as encode(video.to(bf16) / 127.5 - 1.0): the
+        normalisation, the channels-last permute and the 3 -> 16 channel pad are one kernel (cp25_u8_to_clip)
+        writing the encoder's input clip."""
+        if video_u8.dim() != 5 or video_u8.shape[0] != 1 or video_u8.dtype != torch.uint8:
+            raise ValueError(f"encode_u8 takes a uint8 [1, C, T, H, W] video, got {video_u8.dtype} {tuple(video_u8.shape)}")
+        return self._encode_clip(N.u8_to_clip(video_u8[0].to(self.device)))
+
+    def _encode_clip(self, x: torch.Tensor) -> torch.Tensor:
+        """x [T, H, W, 16] bf16 channels-last clip -> mu [1, 16, Tl, H/8, W/8]."""
+        T, H, W, _ = x.shape
         cache = _FeatCache()
         tw = self.temporal_window
         chunks = [x[:1]]
@@ -412,6 +426,20 @@ class WanVAE:
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
         """latent [1, 16, T, h, w] -> video [1, 3, 1 + 4 (T-1), 8h, 8w] bf16."""
+        return self._decode_clip(z).permute(3, 0, 1, 2).unsqueeze(0).contiguous()
+
+    @torch.no_grad()
+    def decode_u8(self, z: torch.Tensor, layout: str = "THWC") -> torch.Tensor:
+        """latent -> uint8 video, [T, H, W, 3] ("THWC") or [1, 3, T, H, W] ("NCTHW"): decode's channels-last
+        result quantised by cp25_clip_to_u8 (trunc(clamp((v + 1) / 2, 0, 1) * 255)), with no NCTHW or fp32 copy."""
+        from .pixels import clip_to_uint8
+
+        if layout not in ("THWC", "NCTHW"):
+            raise ValueError(f"layout must be 'THWC' or 'NCTHW', got {layout!r}")
+        return clip_to_uint8(self._decode_clip(z), layout)
+
+    def _decode_clip(self, z: torch.Tensor) -> torch.Tensor:
+        """latent [1, 16, T, h, w] -> channels-last video [Tp, H, W, 3] bf16 (bands gathered under CP)."""
         assert z.shape[0] == 1, "batch 1"
         _, C, T, h, w = z.shape
         zl = z[0].to(self.device, BF16).permute(1, 2, 3, 0).contiguous()  # [T, h, w, 16]
@@ -437,7 +465,7 @@ class WanVAE:
                 video = allv.permute(1, 0, 2, 3, 4).reshape(video.shape[0], n * video.shape[1], *video.shape[2:])
         finally:
             self._band = None
-        return video.permute(3, 0, 1, 2).unsqueeze(0).contiguous()
+        return video
 
 
 class Wan2pt1VAEInterface:
@@ -459,6 +487,14 @@ class Wan2pt1VAEInterface:
     def decode(self, latent: torch.Tensor) -> torch.Tensor:
         in_dtype = latent.dtype
         return self.model.decode(latent).to(in_dtype)
+
+    def encode_u8(self, video_u8: torch.Tensor) -> torch.Tensor:
+        """uint8 [1, 3, T, H, W] device video -> bf16 latent (WanVAE.encode_u8)."""
+        return self.model.encode_u8(video_u8)
+
+    def decode_u8(self, latent: torch.Tensor, layout: str = "THWC") -> torch.Tensor:
+        """latent -> uint8 device video [T, H, W, 3] ("THWC") or [1, 3, T, H, W] ("NCTHW") (WanVAE.decode_u8)."""
+        return self.model.decode_u8(latent, layout)
 
     def get_latent_num_frames(self, num_pixel_frames: int) -> int:
         return 1 + (num_pixel_frames - 1) // 4

@@ -476,6 +476,44 @@ int cp25_softmax_rows(const float* s, int64_t rows, int cols, int64_t ld_s, floa
 int cp25_quant_fp8_rows(const void* x, void* q, float* scale, int64_t n_rows, int64_t k, hipStream_t stream);
 int cp25_gelu_quant_fp8(const void* x, void* q, float* scale, int64_t n_rows, int64_t k, hipStream_t stream);
 
+/* ---------------------------------------------------------------- pixels (uint8 frames <-> the VAE's clips)
+ * Strides are in elements of the tensor's own type and may describe planar or channels-last memory.
+ *
+ * cp25_resize_crop_u8: antialiased bilinear resize fused with the centre crop, on N uint8 frames of C <= 4 channels.
+ * src is indexed by src_strides = (n, c, y, x) over [N][C][Hin][Win]; dst points at the first pixel of the th x tw
+ * crop window and is indexed by dst_strides = (n, c, y, x). The separable triangle filter comes as per-axis device
+ * tables over the full resized extent (rh, rw): start[out] (first source index), count[out] (taps used, <= taps) and
+ * w[out][taps] fp32 (rows sum to 1), with start non-decreasing; the window is rows [top, top + th) x columns
+ * [left, left + tw) of that extent and only the window is computed. Per output pixel: an fp32 sum over the taps in
+ * ascending x for each source row (kept fp32), an fp32 sum of those over the rows in ascending y, rint (half to
+ * even), clamp to [0, 255]; the order is fixed, so a pixel's value depends on neither the tile, the window nor the
+ * layout. One launch: a workgroup stages the source bytes of its 8 x 32 output tile in LDS (dword loads where a
+ * row's bytes are contiguous and aligned), writes the horizontal pass to an fp32 LDS tile and runs the vertical pass
+ * from it; no intermediate in HBM. Reads stay inside [0, Hin) x [0, Win) of a frame, writes inside the window.
+ * Supported: Hin <= 4 rh and Win <= 4 rw (downscale by at most 4; any upscale), taps in [1, 9]; else CP25_ERR_INVAL
+ * before any launch. Replaces: resize_input (inference/video2world.py:75-97: torchvision resize + center_crop). */
+int cp25_resize_crop_u8(const void* src, const int64_t* src_strides, int N, int C, int Hin, int Win, void* dst,
+                        const int64_t* dst_strides, const int32_t* y_start, const int32_t* y_count, const float* y_w,
+                        int y_taps, const int32_t* x_start, const int32_t* x_count, const float* x_w, int x_taps, int rh,
+                        int rw, int top, int left, int th, int tw, hipStream_t stream);
+
+/* uint8 video, indexed by src_strides = (c, t, y, x) over [C][T][H][W], C <= 16 -> the VAE encoder's contiguous
+ * channels-last clip dst [T][H][W][16] bf16 (16-B aligned): channel c < C = bf16(float(bf16(float(u) / 127.5f)) -
+ * 1.0f), the two bf16 roundings of `video.to(bfloat16) / 127.5 - 1.0`; channels >= C are written as zeros.
+ * Replaces: _normalize_video_databatch_inplace (text2world_model_rectified_flow.py:735-736) and the NCTHW ->
+ * channels-last permute and 3 -> 16 channel pad in front of the encoder. */
+int cp25_u8_to_clip(const void* src, const int64_t* src_strides, int C, int T, int H, int W, void* dst,
+                    hipStream_t stream);
+
+/* bf16 clip indexed by src_strides = (t, y, x, c) over [T][H][W][C], C <= 4 (the decoder's channels-last output) ->
+ * uint8 indexed by dst_strides = (t, y, x, c): u = trunc(clamp((float(v) + 1) / 2, 0, 1) * 255) in fp32. On every
+ * non-NaN bf16 value this equals the reference's three quantisations: the autoregressive write-back
+ * ((v / 2 + 0.5).clamp(0, 1) * 255).to(uint8) (inference/video2world.py:796-804), (clamp((v + 1) / 2, 0, 1) *
+ * 255).to(uint8) of the action loop and (((1 + v) / 2) * 255).clamp(0, 255).to(uint8) of save_video. NaN input is
+ * unspecified. */
+int cp25_clip_to_u8(const void* src, const int64_t* src_strides, int T, int H, int W, int C, void* dst,
+                    const int64_t* dst_strides, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,13 +31,15 @@ def main():
                     help="replay each chunk's DiT forward from a HIP graph after its first evaluation (model.hip_graph)")
     ap.add_argument("--block-gemm", default="own", choices=("own", "lib"),
                     help="block projections on the hand-written GEMMs (default) or the library (A/B)")
+    ap.add_argument("--pixel-path", default="host", choices=("host", "device"),
+                    help="device: conditioning frames and decoded chunks stay uint8 on the GPU (cosmos_predict2/pixels.py)")
     a = ap.parse_args()
     h, w = (int(x) for x in a.resolution.split(","))
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     n_chunks = -(-(a.frames - 1) // a.chunk_size)
     inf = ActionConditionedInference(device=dev, state_t=1 + a.chunk_size // 4, linear_precision=a.linear_precision,
-                                     attention_precision=a.attention_precision)
+                                     attention_precision=a.attention_precision, pixel_path=a.pixel_path)
     if a.block_gemm == "lib":
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         from library_gemm_net import use_library_gemms
@@ -58,7 +60,7 @@ def main():
     print(json.dumps({"workload": f"action-conditioned AR {a.frames}f at {h}x{w}, {n_chunks} chunks of "
                                   f"{a.chunk_size + 1} frames, {a.num_steps} UniPC steps, CFG 7",
                       "linear_precision": a.linear_precision, "block_gemm": a.block_gemm, "hip_graph": a.hip_graph,
-                      "attention_precision": a.attention_precision, "n_gpus": 1, "seconds": dt,
+                      "attention_precision": a.attention_precision, "pixel_path": a.pixel_path, "n_gpus": 1, "seconds": dt,
                       "frames_per_s": a.frames / dt, "s_per_chunk": dt / n_chunks}), flush=True)
 
 
