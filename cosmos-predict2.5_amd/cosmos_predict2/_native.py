@@ -61,7 +61,8 @@ _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I = ctypes.c_int
 _F = ctypes.c_float
-_T = ctypes.POINTER(CP25Tensor)
+_D = ctypes.c_double
+_T =ctypes.POINTER(CP25Tensor)
 
 # symbol -> argtypes (restype int, except the *_workspace_bytes queries)
 SIGNATURES = {
@@ -111,6 +112,8 @@ SIGNATURES = {
     "cp25_patchify": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _P],
     "cp25_patchify_ld": [_P, _P, _P, _P, _P, _I64, _I64, _I64, _I64, _P],
     "cp25_cfg_velocity": [_P, _I, _P, _P, _P, _F, _I, _P, _I64, _I64, _I64, _P],
+    "cp25_trig_patchify_ld": [_P, _P, _P, _P, _D, _P, _P, _I64, _I64, _I64, _I64, _P],
+    "cp25_trig_x0_step": [_P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _I, _I64, _I64, _I64, _P],
     "cp25_unipc_step": [_P, _P, _P, _P, _P, _I64, ctypes.POINTER(UniPCParams), _P],
     "cp25_conv3d": [ctypes.POINTER(ctypes.c_void_p), _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                     _I, _I, _I, _I, _I, _I, _P],
@@ -829,6 +832,61 @@ def cfg_velocity(net: torch.Tensor, noise: Optional[torch.Tensor], gt: Optional[
                                _ptr(out), n_tok, tok0, hw, _stream(net.device))
     _check("cp25_cfg_velocity", rc)
     return out
+
+
+def _check_frame_table(name: str, tab: torch.Tensor, frame_mask: torch.Tensor) -> None:
+    """A float64 per-frame coefficient table of the TrigFlow kernels: indexed like the mask, so as long as it."""
+    if tab.dtype != torch.float64 or tab.dim() != 1 or not tab.is_contiguous() or tab.numel() != frame_mask.numel():
+        raise ValueError(f"{name} must be a contiguous float64 [{frame_mask.numel()}] table (one entry per mask frame), "
+                         f"got {tab.dtype} {tuple(tab.shape)}")
+
+
+def _check_patch_rows(name: str, t: torch.Tensor, n_tok: int) -> None:
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n_tok * 64:
+        raise ValueError(f"{name} must be contiguous fp32 with {n_tok} x 64 elements, got {t.dtype} {tuple(t.shape)}")
+
+
+def trig_patchify(xs: torch.Tensor, gt: Optional[torch.Tensor], frame_mask: torch.Tensor, c_in: torch.Tensor,
+                  sigma_data: float, pad_mask: Optional[torch.Tensor], *, tok0: int, hw: int,
+                  ld: int = 72) -> torch.Tensor:
+    """The distilled student's x_embedder input rows [n_tok, 72] bf16 (cp25_trig_patchify_ld): patchify's rows with
+    channels 0..15 = bf16(float((gt / sigma_data) * mask + (x * c_in[frame]) * (1 - mask))) in fp64. c_in: float64
+    [frames] on the device. ld as in patchify (128: the own GEMM's zero-padded K = 128 operand)."""
+    lib = load_library()
+    n_tok = xs.shape[0]
+    _check_mask(frame_mask, n_tok=n_tok, tok0=tok0, hw=hw)
+    _check_frame_table("c_in", c_in, frame_mask)
+    _check_patch_rows("xs", xs, n_tok)
+    if gt is not None:
+        _check_patch_rows("gt", gt, n_tok)
+    out = torch.empty((n_tok, ld), dtype=torch.bfloat16, device=xs.device)
+    rc = lib.cp25_trig_patchify_ld(_ptr(xs), _ptr(gt), _ptr(frame_mask), _ptr(c_in), float(sigma_data),
+                                   _ptr(pad_mask), _ptr(out), int(ld), n_tok, tok0, hw, _stream(xs.device))
+    _check("cp25_trig_patchify_ld", rc)
+    return out[:, :72]
+
+
+def trig_x0_step(xs: torch.Tensor, net: torch.Tensor, noise: Optional[torch.Tensor], gt: Optional[torch.Tensor],
+                 frame_mask: torch.Tensor, c_skip: torch.Tensor, c_out: torch.Tensor, *, replace_gt: bool,
+                 sigma_data: float, cos_next: float, sin_next: float, last: bool, tok0: int, hw: int) -> torch.Tensor:
+    """One distilled-student update in place on the fp32 state xs [n_tok, 64] (cp25_trig_x0_step): x0 = c_skip x +
+    c_out net in fp64 (+ GT-frame replacement), then the TrigFlow re-noising to the next time, or nan_to_num(x0) at the
+    last step. net: [n_tok, 1, 64] fp32; c_skip / c_out: float64 [frames] on the device. Returns xs."""
+    lib = load_library()
+    n_tok = xs.shape[0]
+    _check_mask(frame_mask, n_tok=n_tok, tok0=tok0, hw=hw)
+    _check_frame_table("c_skip", c_skip, frame_mask)
+    _check_frame_table("c_out", c_out, frame_mask)
+    for name, t in (("xs", xs), ("net", net), ("noise", noise), ("gt", gt)):
+        if t is not None:
+            _check_patch_rows(name, t, n_tok)
+    if not last and noise is None:
+        raise ValueError("trig_x0_step needs the noise unless last=True")
+    rc = lib.cp25_trig_x0_step(_ptr(xs), _ptr(net), _ptr(noise), _ptr(gt), _ptr(frame_mask), _ptr(c_skip), _ptr(c_out),
+                               int(bool(replace_gt)), float(sigma_data), float(cos_next), float(sin_next),
+                               int(bool(last)), n_tok, tok0, hw, _stream(xs.device))
+    _check("cp25_trig_x0_step", rc)
+    return xs
 
 
 def unipc_step(x: torch.Tensor, v: torch.Tensor, m0: torch.Tensor, m1: torch.Tensor, last: torch.Tensor,

@@ -1172,7 +1172,13 @@ class MinimalV1LVGDiT:
         if not cfg.use_wan_fp32_strategy:
             # FinalLayer without the fp32 autocast (minimal_v4_dit.py:974-995): LayerNorm, * (1 + scale), + shift as
             # bf16 ops (cp25_ln_mod's arithmetic, with the last residual) and a bf16 linear on the own GEMM
-            x_new = torch.empty((n, B, D), dtype=BF16, device=self.device) if y is not None else None
+            x_new = None
+            if y is not None:
+                # an unfused last MLP residual rides in this LN-mod, which reads shift / scale / gate through one pair
+                # of strides: the gate is a column block of the [B, T, 3D] block modulation, shift / scale are halves of
+                # the [B, T, 2D] final modulation, so the three ([B, T, D] each, a few rows) are copied into one layout
+                x_new = torch.empty((n, B, D), dtype=BF16, device=self.device)
+                shift_f, scale_f, gate_prev = torch.stack([shift_f, scale_f, gate_prev]).unbind(0)
             h = N.ln_mod(x, shift_f, scale_f, x_st=B * D, x_sb=D, y=y, gate=gate_prev, x_out=x_new, **common)
             out = N.gemm_epi(h.view(n * B, D), self.w_final_bf16)[:, : self.w_final.shape[0]].float()
             return out.view(n, B, -1)

@@ -11,6 +11,11 @@ parallel rank owns a contiguous token range. One sampler step is
     -> GT-frame velocity replacement + CFG (HIP, reads the final layer's output in place)
     -> fused UniPC corrector/predictor update (HIP)
 with the only inter-GPU traffic the K/V all-gather inside self-attention.
+
+A model whose SamplerConfig.sampler is "dmd2" samples with the DMD2-distilled few-step student instead
+(DistilledSamplingRun; reference: distill/models/video2world_model_distill_dmd2.py:421-492 and denoise_edm,
+video2world_model_rectified_flow.py:214-346): TrigFlow preconditioning + patchify (HIP) -> one DiT forward at B = 1
+-> x0 reconstruction + re-noising (HIP), four times, with no CFG and no solver history.
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ import torch
 
 from . import _native as N
 from . import context_parallel as cpu
+from . import trigflow
 from .dit import Geometry, MinimalV1LVGDiT
 from .net_config import DiTConfig, SamplerConfig
 from .scheduler import FlowUniPCMultistepScheduler
@@ -102,13 +108,29 @@ class Video2WorldModelRectifiedFlow:
 
     # ------------------------------------------------------------------ the sampler
     @torch.no_grad()
-    def begin_sampling(self, gt: Optional[torch.Tensor], ctx_cond: torch.Tensor, ctx_uncond: torch.Tensor, *,
+    def begin_sampling(self, gt: Optional[torch.Tensor], ctx_cond: torch.Tensor,
+                       ctx_uncond: Optional[torch.Tensor], *,
                        state_shape, num_conditional_frames: int, guidance: float, seed: int, num_steps: int,
                        shift: float = 5.0, cfg_mode: Optional[str] = None, net_fn=None,
                        action: Optional[torch.Tensor] = None,
-                       view_indices: Optional[torch.Tensor] = None) -> "SamplingRun":
+                       view_indices: Optional[torch.Tensor] = None,
+                       init_noise: Optional[torch.Tensor] = None) -> "SamplingRun":
         """Set up one trajectory of the sampling loop (text2world_model_rectified_flow.py:556-582):
-        noise, schedule, conditioning; SamplingRun.step() then runs one loop iteration (:584-594)."""
+        noise, schedule, conditioning; SamplingRun.step() then runs one loop iteration (:584-594).
+        A model whose config.sampler is "dmd2" returns the distilled student's DistilledSamplingRun instead (same
+        interface): ctx_uncond, guidance, shift and cfg_mode are accepted and unused there (teacher guidance is
+        distilled into the student: video2world_model_distill_dmd2.py:371), init_noise is that loop's own argument."""
+        if self.config.sampler == "dmd2":
+            if action is not None or view_indices is not None:
+                raise ValueError("the distilled (dmd2) sampler serves the plain video2world student: no `action` "
+                                 "and no `view_indices`")
+            return DistilledSamplingRun(self, gt, ctx_cond, state_shape=state_shape,
+                                        num_conditional_frames=num_conditional_frames, seed=seed,
+                                        num_steps=num_steps, net_fn=net_fn, init_noise=init_noise)
+        if self.config.sampler != "unipc":
+            raise ValueError(f"unknown SamplerConfig.sampler {self.config.sampler!r} ('unipc' or 'dmd2')")
+        if init_noise is not None:
+            raise ValueError("`init_noise` is the distilled (dmd2) sampler's argument")
         return SamplingRun(self, gt, ctx_cond, ctx_uncond, state_shape=state_shape,
                            num_conditional_frames=num_conditional_frames, guidance=guidance, seed=seed,
                            num_steps=num_steps, shift=shift, cfg_mode=cfg_mode, net_fn=net_fn, action=action,
@@ -119,14 +141,17 @@ class Video2WorldModelRectifiedFlow:
                        state_shape, num_conditional_frames: int, guidance: float, seed: int, num_steps: int,
                        shift: float = 5.0, cfg_mode: Optional[str] = None, progress=None,
                        net_fn=None, action: Optional[torch.Tensor] = None,
-                       view_indices: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       view_indices: Optional[torch.Tensor] = None,
+                       init_noise: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Core loop. gt: x0 latent [1, C, T, H, W] fp32 (or None when no frame is conditioned);
         ctx_*: text embeddings [1, Lctx, proj_in]. Returns latents [1, C, T, H, W] fp32.
-        net_fn(rows [n,1,72] bf16, t_B_T [2,T] fp32, geo) -> [n,2,64] replaces the DiT (tests only)."""
+        net_fn(rows [n,1,72] bf16, t_B_T [2,T] fp32, geo) -> [n,2,64] replaces the DiT (tests only).
+        With config.sampler == "dmd2" this runs the distilled student's loop (DistilledSamplingRun: one branch, so
+        net_fn sees t_B_T [1,T] and returns [n,1,64]; ctx_uncond may be None)."""
         run = self.begin_sampling(gt, ctx_cond, ctx_uncond, state_shape=state_shape,
                                   num_conditional_frames=num_conditional_frames, guidance=guidance, seed=seed,
                                   num_steps=num_steps, shift=shift, cfg_mode=cfg_mode, net_fn=net_fn,
-                                  action=action, view_indices=view_indices)
+                                  action=action, view_indices=view_indices, init_noise=init_noise)
         while not run.done:
             i = run.step()
             if progress is not None:
@@ -162,6 +187,12 @@ class Video2WorldModelRectifiedFlow:
         if n_cond > 0:
             gt = self.encode_conditioning(video, n_cond, state_shape[1])
         ctx_c = data_batch["t5_text_embeddings"]
+        if self.config.sampler == "dmd2":
+            # one branch, no CFG: no unconditional context is built or prepared (get_x0_fn_from_batch,
+            # video2world_model_distill_dmd2.py:364-418, uses the condition alone)
+            return self.begin_sampling(gt, ctx_c, None, state_shape=state_shape, num_conditional_frames=n_cond,
+                                       guidance=guidance, seed=seed, num_steps=num_steps, shift=shift,
+                                       action=data_batch.get("action"))
         if is_negative_prompt and isinstance(data_batch.get("neg_t5_text_embeddings"), torch.Tensor):
             ctx_u = data_batch["neg_t5_text_embeddings"]
         else:
@@ -215,16 +246,12 @@ class Video2WorldModelRectifiedFlow:
         return out
 
 
-class SamplingRun:
-    """One sampler trajectory of Video2WorldModelRectifiedFlow, advanced one evaluation at a time.
+class _TokenState:
+    """What both sampling runs hold per trajectory: the token geometry and this rank's CP shard of it, the noise, the
+    conditioning-frame mask and the ground-truth latent in patch layout, and the gather back to [1, C, T, H, W]."""
 
-    Setup = text2world_model_rectified_flow.py:556-582 (noise, schedule, conditioning); step() = one
-    iteration of the loop at :584-594 (patchify + frame replacement, the CFG-batched DiT forward,
-    GT-frame velocity replacement + CFG, fused UniPC update); latents() = :596-599 (CP gather)."""
-
-    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt, ctx_cond, ctx_uncond, *, state_shape,
-                 num_conditional_frames: int, guidance: float, seed: int, num_steps: int, shift: float = 5.0,
-                 cfg_mode: Optional[str] = None, net_fn=None, action=None, view_indices=None):
+    def _setup_state(self, model: "Video2WorldModelRectifiedFlow", gt, state_shape, num_conditional_frames: int,
+                     seed: int, init_noise: Optional[torch.Tensor] = None) -> None:
         self.model = model
         C, T, H, W = state_shape
         self.state_shape = (C, T, H, W)
@@ -245,7 +272,12 @@ class SamplingRun:
             sl = slice(geo.tok0, geo.tok0 + geo.n_tok)
         self.geo, self.cp, self.world = geo, cp, world
 
-        noise_full = arch_invariant_rand((1, C, T, H, W), torch.float32, dev, seed)
+        if init_noise is None:
+            noise_full = arch_invariant_rand((1, C, T, H, W), torch.float32, dev, seed)
+        else:
+            if tuple(init_noise.shape) != (1, C, T, H, W):
+                raise ValueError(f"init_noise {tuple(init_noise.shape)} is not the state shape {(1, C, T, H, W)}")
+            noise_full = init_noise.to(dev, torch.float32)
         self.noise = to_patch_layout(noise_full[0])[sl].contiguous()
         del noise_full
         frame_mask = torch.zeros(T, dtype=torch.float32, device=dev)
@@ -261,6 +293,37 @@ class SamplingRun:
         self.gtp = None
         if gt is not None and num_conditional_frames > 0:
             self.gtp = to_patch_layout(gt[0].to(dev, torch.float32))[sl].contiguous()
+
+    @torch.no_grad()
+    def latents(self) -> torch.Tensor:
+        """The current latent state [1, C, T, H, W] fp32 (all-gathered over the CP group)."""
+        x = self.x
+        if self.world > 1:
+            x = cpu.gather_tokens(x, self.cp)
+            if self.geo.frames is not None:  # frame-sharded ranks: back to the global (view, frame, h, w) order
+                C_, T_, H_, W_ = self.state_shape
+                g = self.geo
+                ids = torch.cat([Geometry.frame_shard(T_, g.Hp, g.Wp, g.n_views, r, self.world).token_ids(x.device)
+                                 for r in range(self.world)])
+                xg = torch.empty_like(x)
+                xg[ids] = x
+                x = xg
+        _, T, H, W = self.state_shape
+        return from_patch_layout(x, T, H, W).unsqueeze(0)
+
+
+class SamplingRun(_TokenState):
+    """One sampler trajectory of Video2WorldModelRectifiedFlow, advanced one evaluation at a time.
+
+    Setup = text2world_model_rectified_flow.py:556-582 (noise, schedule, conditioning); step() = one
+    iteration of the loop at :584-594 (patchify + frame replacement, the CFG-batched DiT forward,
+    GT-frame velocity replacement + CFG, fused UniPC update); latents() = :596-599 (CP gather)."""
+
+    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt, ctx_cond, ctx_uncond, *, state_shape,
+                 num_conditional_frames: int, guidance: float, seed: int, num_steps: int, shift: float = 5.0,
+                 cfg_mode: Optional[str] = None, net_fn=None, action=None, view_indices=None):
+        self._setup_state(model, gt, state_shape, num_conditional_frames, seed)
+        dev, geo, world = model.device, self.geo, self.world
 
         self.net_fn = net_fn
         self.ctx = None if net_fn is not None else model.net.prepare_context(torch.cat([ctx_cond, ctx_uncond], 0))
@@ -341,19 +404,78 @@ class SamplingRun:
         self.i += 1
         return self.i - 1
 
+
+class DistilledSamplingRun(_TokenState):
+    """One trajectory of the DMD2-distilled few-step student (config.sampler == "dmd2"), SamplingRun's interface.
+
+    Setup and loop = Video2WorldModelDistillDMD2TrigFlow.generate_samples_from_batch (distill/models/
+    video2world_model_distill_dmd2.py:421-492) around denoise_edm with net_type "student" (models/
+    video2world_model_rectified_flow.py:214-346). The times are selected_sampling_time[:num_steps] + [0] (:482-484),
+    so num_steps = 35 runs all four. One step() at time t_cur is
+        trig_patchify (HIP): xt * c_in, conditioning frames gt / sigma_data, the net-dtype cast, the patch rows
+        -> one DiT forward at B = 1 on the text context alone (no CFG: the teacher's guidance is distilled in, :371)
+        -> trig_x0_step (HIP): x0 = c_skip xt + c_out net, GT frames replaced, then the re-noising
+           cos(t_next) x0 / sigma_data + sin(t_next) noise, or nan_to_num(x0) once t_next <= 1e-5.
+    The reference holds the state in float64 between the steps and enters the denoiser with x.float() (:486); here
+    the state is that fp32 tensor and the kernels do the float64 arithmetic. The per-frame float64 tables (trigflow.py)
+    are a few numbers per step, made on the host when the run is set up.
+    Noise: `init_noise` [1, C, T, H, W] as the reference's argument, else this build's arch_invariant_rand(seed) (the
+    reference draws from a device torch.Generator, whose stream is not portable: DESIGN.md §4).
+    model.hip_graph is not used: four evaluations are not launch-bound."""
+
+    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt, ctx, *, state_shape, num_conditional_frames: int,
+                 seed: int, num_steps: int, net_fn=None, init_noise: Optional[torch.Tensor] = None):
+        cfg = model.config
+        times = trigflow.step_times(cfg.selected_sampling_time, num_steps)
+        self._setup_state(model, gt, state_shape, num_conditional_frames, seed, init_noise)
+        dev, geo = model.device, self.geo
+        self.net_fn = net_fn
+        self.ctx = None if net_fn is not None else model.net.prepare_context(ctx)
+        self.replace_gt = bool(cfg.denoise_replace_gt_frames)
+        self.sigma_data = float(cfg.sigma_data)
+        mask_host = self.frame_mask.cpu()
+        own = None if geo.frames is None else list(geo.frames)  # a frame-sharded rank's rows of the tables (kmask)
+        self.steps = []
+        for t_cur, t_next in zip(times[:-1], times[1:]):
+            tf = trigflow.frame_times(t_cur, mask_host, cfg.sigma_conditional, cfg.sigma_data)
+            c_skip, c_out, c_in, c_noise = trigflow.trig_scaling(tf, cfg.trig_scaling, cfg.sigma_data)
+            if cfg.change_time_embed:
+                c_noise = tf
+            tabs = [c if own is None else c[own].contiguous() for c in (c_skip, c_out, c_in)]
+            cos_next, sin_next, last = trigflow.renoise_scalars(t_next)
+            self.steps.append(dict(c_skip=tabs[0].to(dev), c_out=tabs[1].to(dev), c_in=tabs[2].to(dev),
+                                   t_B_T=trigflow.net_timesteps(c_noise, model.net_cfg.timestep_scale).to(dev),
+                                   cos_next=cos_next, sin_next=sin_next, last=last))
+        self.restart()
+
+    def restart(self) -> None:
+        """Back to the first time from the same noise."""
+        self.x = self.noise.clone()
+        self.i = 0
+
+    @property
+    def num_evals(self) -> int:
+        return len(self.steps)
+
+    @property
+    def done(self) -> bool:
+        return self.i >= len(self.steps)
+
     @torch.no_grad()
-    def latents(self) -> torch.Tensor:
-        """The current latent state [1, C, T, H, W] fp32 (all-gathered over the CP group)."""
-        x = self.x
-        if self.world > 1:
-            x = cpu.gather_tokens(x, self.cp)
-            if self.geo.frames is not None:  # frame-sharded ranks: back to the global (view, frame, h, w) order
-                C_, T_, H_, W_ = self.state_shape
-                g = self.geo
-                ids = torch.cat([Geometry.frame_shard(T_, g.Hp, g.Wp, g.n_views, r, self.world).token_ids(x.device)
-                                 for r in range(self.world)])
-                xg = torch.empty_like(x)
-                xg[ids] = x
-                x = xg
-        _, T, H, W = self.state_shape
-        return from_patch_layout(x, T, H, W).unsqueeze(0)
+    def step(self) -> int:
+        """One student evaluation and its state update; returns its index."""
+        if self.done:
+            raise RuntimeError("the trajectory is complete (restart() to run it again)")
+        m, geo, s = self.model, self.geo, self.steps[self.i]
+        rows = N.trig_patchify(self.x, self.gtp, self.kmask, s["c_in"], self.sigma_data, None, tok0=geo.tok0,
+                               hw=geo.hw, ld=128)
+        if self.net_fn is None:
+            net_out = m.net.forward_tokens(rows.view(geo.n_tok, 1, -1), s["t_B_T"], self.ctx, geo, rows_k128=True)
+        else:
+            net_out = self.net_fn(rows.view(geo.n_tok, 1, -1), s["t_B_T"], geo)
+        N.trig_x0_step(self.x, net_out.contiguous(), self.noise, self.gtp, self.kmask, s["c_skip"], s["c_out"],
+                       replace_gt=self.replace_gt, sigma_data=self.sigma_data, cos_next=s["cos_next"],
+                       sin_next=s["sin_next"], last=s["last"], tok0=geo.tok0, hw=geo.hw)
+        del net_out
+        self.i += 1
+        return self.i - 1

@@ -12,6 +12,7 @@ Values follow the reference's registered configs:
 from __future__ import annotations
 
 import dataclasses
+import math
 from dataclasses import dataclass, field
 
 
@@ -105,6 +106,17 @@ class SamplerConfig:
     denoise_replace_gt_frames: bool = True
     cfg_mode: str = "video2world"  # "video2world": c + g(c-u) ; "text2world": u + g(c-u)
     resolution: str = "720"
+    # "unipc": the rectified-flow loop above. "dmd2": the distilled few-step student loop in the TrigFlow
+    # parameterisation (distill/models/video2world_model_distill_dmd2.py:421-492 around denoise_edm,
+    # models/video2world_model_rectified_flow.py:214-346): one single-branch evaluation per selected time, no CFG, no
+    # solver history (model.DistilledSamplingRun). The fields below are read by that loop only
+    # (Video2WorldModelDistillationConfigDMD2TrigFlow :60-82 and the BaseDistillConfig fields it inherits).
+    sampler: str = "unipc"
+    selected_sampling_time: tuple = ()  # TrigFlow times, descending from pi / 2; the loop appends the final 0
+    trig_scaling: str = "rectified_flow"  # config.scaling: "rectified_flow" or "edm" (denoiser_scaling.py)
+    sigma_data: float = 1.0
+    sigma_conditional: float = 1e-4  # noise level of the conditioning frames: t_cond = atan(sigma_conditional / sigma_data)
+    change_time_embed: bool = False  # the student's c_noise(t) = t (denoise_edm :268-270)
 
 
 DIT_2B = DiTConfig()
@@ -139,6 +151,25 @@ DIT_2B_MULTIVIEW_CROSSVIEW = DIT_2B.replace(n_cameras_emb=7, view_condition_dim=
                                             rope_t_extrapolation_ratio=8.0 / 24.0, adaln_view_embedding=True,
                                             cross_view_attn_map=CROSS_VIEW_MAP_7, use_wan_fp32_strategy=False)
 
+# DMD2-distilled 4-step student (distill/configs/experiment/experiments_dmd2_trigflow.py:163-193, the base config of
+# experiment dmd2_trigflow_distill_cosmos_predict2_2B_bidirectional :266-286, and the config class
+# distill/models/video2world_model_distill_dmd2.py:60-82): times (pi / 2, atan 15, atan 5, atan 5/3) = rectified-flow t 1, 0.75, 0.5, 0.25 under shift 5 (:179, :80-81),
+# scaling "rectified_flow" (:166), sigma_data 1 (:181), sigma_conditional 1e-4 (:180), state_t 24 (:182), resolution
+# "720" (:164); denoise_replace_gt_frames True is Video2WorldConfig's default (models/video2world_model.py:52), which
+# the config class inherits, and change_time_embed is left at its False default.
+# The student net is distill/configs/defaults/net.py:32-57 (COSMOS_V1_2B_NET: MinimalV1LVGDiT, the 2B layout; hydra net
+# "cosmos_v1_2B_student", :82, selected at experiments_dmd2_trigflow.py:60) with the experiment's net=dict(...) (:118-128: RoPE h/w 3.0, t 1.0, no fps modulation, crossattn projection from 100352).
+# Neither sets timestep_scale nor use_wan_fp32_strategy, so MinimalV1LVGDiT's and MiniTrainDIT's own defaults hold:
+# timestep_scale 1.0 (networks/minimal_v1_lvg_dit.py:25) and use_wan_fp32_strategy False (networks/minimal_v4_dit.py:
+# 1352): c_noise in [0, 1] reaches the embedder unscaled and the t-embedding, AdaLN and final layer run in bf16
+# (MinimalV1LVGDiT._time_modulation_bf16), unlike the rectified-flow experiments' overrides (0.001, True).
+# crossattn_emb_channels 1024 is MiniTrainDIT's default (:1328).
+DIT_2B_DISTILLED = DIT_2B.replace(timestep_scale=1.0, use_wan_fp32_strategy=False)
+SAMPLER_2B_DISTILLED = SamplerConfig(sampler="dmd2",
+                                     selected_sampling_time=(math.pi / 2, math.atan(15), math.atan(5), math.atan(5 / 3)),
+                                     trig_scaling="rectified_flow", sigma_data=1.0, sigma_conditional=0.0001,
+                                     state_t=24, denoise_replace_gt_frames=True, resolution="720")
+
 # model name (cosmos_predict2/config.py ModelKey.name) -> (net, sampler)
 MODELS = {
     "2B/post-trained": (DIT_2B, SAMPLER_2B_POST_TRAINED),
@@ -148,6 +179,9 @@ MODELS = {
     "2B/auto/multiview": (DIT_2B_MULTIVIEW, SAMPLER_MULTIVIEW),
     # the reference registers this net (hydra net "cosmos_v1_2B_multiview_crossview") but ships no checkpoint for it
     "2B/auto/multiview-crossview": (DIT_2B_MULTIVIEW_CROSSVIEW, SAMPLER_MULTIVIEW),
+    # the reference ships the distillation recipe and the student's inference loop but no checkpoint key for a
+    # distilled model (checkpoint_db.py has none): this entry serves a student distilled with that recipe
+    "2B/distilled": (DIT_2B_DISTILLED, SAMPLER_2B_DISTILLED),
 }
 
 # Subset of VIDEO_RES_SIZE_INFO (cosmos_predict2/_src/predict2/datasets/utils.py:44-67); the model's

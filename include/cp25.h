@@ -392,6 +392,39 @@ int cp25_cfg_velocity(const float* net, int B, const float* noise, const float* 
                       float guidance, int cfg_mode, float* v_out, int64_t n_tok, int64_t tok0, int64_t hw,
                       hipStream_t stream);
 
+/* ---------------------------------------------------------------- distilled (DMD2 / TrigFlow) student steps
+ * The few-step student loop (distill/models/video2world_model_distill_dmd2.py:421-492) around its denoiser
+ * (models/video2world_model_rectified_flow.py:214-346, net_type "student"). Both kernels work on the patch layout
+ * above, index their per-frame tables (frame_mask fp32, c_* float64, one entry per latent frame) by (tok0 + tok) / hw
+ * as cp25_patchify does, and compute in fp64 as the reference's float64 state and coefficients make PyTorch do, one
+ * IEEE operation per torch op (no contraction). The masks are used arithmetically, a * mask + b * (1 - mask), as
+ * written there. xs / gt / net / noise / out 16-B aligned (four fp32 move at once), the float64 tables 8-B aligned,
+ * sigma_data > 0; -22 otherwise.
+ *
+ * cp25_trig_patchify_ld: cp25_patchify_ld's rows (feature order, mask channel 16, pad channel 17, columns 72 ..
+ * out_ld - 1 zeroed; out_ld >= 72, a multiple of 8) with channels 0..15 = (gt / sigma_data) * mask + (x * c_in[frame])
+ * * (1 - mask) in fp64 (x * c_in[frame] when gt == NULL: no conditioning), rounded float64 -> float32 -> bf16, the two
+ * roundings of `tensor.to(torch.bfloat16)` on a float64 tensor.
+ * Replaces: video2world_model_rectified_flow.py:262-266 (scaling, net_state_in = xt * c_in), :274-301 (conditioning
+ * frames / sigma_data, frame replacement), :304 (the cast) plus cp25_patchify_ld's sources. */
+int cp25_trig_patchify_ld(const float* xs, const float* gt, const float* frame_mask, const double* c_in,
+                          double sigma_data, const void* pad_mask, void* out, int64_t out_ld, int64_t n_tok,
+                          int64_t tok0, int64_t hw, hipStream_t stream);
+
+/* In place on the fp32 state xs [n_tok, 64], from the student net's output net [n_tok, 1, 64] fp32 (the layout
+ * cp25_cfg_velocity reads at B = 1):
+ *   x0 = c_skip[frame] * double(xs) + c_out[frame] * double(net)                              (:325-328)
+ *   replace_gt != 0 and gt != NULL: x0 = double(gt) * mask + x0 * (1 - mask)                  (:331-336)
+ *   last == 0: xs = float((cos_next * x0) / sigma_data + double(float(sin_next) * noise))     (dmd2 :486-488)
+ *   last != 0: xs = nan_to_num(float(x0)): NaN -> 0, +-inf -> +-FLT_MAX                       (dmd2 :489-492)
+ * The division is an fp64 division (sigma_data need not be a power of two). `math.sin(t_next) * init_noise` is a
+ * python scalar times a float32 tensor, which PyTorch evaluates in fp32 before the float64 sum widens it: hence
+ * float(sin_next) * noise. noise may be NULL when last != 0; gt, frame_mask may be NULL when nothing is replaced.
+ * Replaces: video2world_model_rectified_flow.py:322-336 and video2world_model_distill_dmd2.py:485-492. */
+int cp25_trig_x0_step(float* xs, const float* net, const float* noise, const float* gt, const float* frame_mask,
+                      const double* c_skip, const double* c_out, int replace_gt, double sigma_data, double cos_next,
+                      double sin_next, int last, int64_t n_tok, int64_t tok0, int64_t hw, hipStream_t stream);
+
 /* ---------------------------------------------------------------- UniPC sampler update
  * Host-computed fp32 coefficients of one FlowUniPCMultistepScheduler.step. */
 typedef struct cp25_unipc_params {
