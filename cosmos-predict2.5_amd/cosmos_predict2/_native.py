@@ -114,6 +114,9 @@ SIGNATURES = {
     "cp25_cfg_velocity": [_P, _I, _P, _P, _P, _F, _I, _P, _I64, _I64, _I64, _P],
     "cp25_trig_patchify_ld": [_P, _P, _P, _P, _D, _P, _P, _I64, _I64, _I64, _I64, _P],
     "cp25_trig_x0_step": [_P, _P, _P, _P, _P, _P, _P, _I, _D, _D, _D, _I, _I64, _I64, _I64, _P],
+    "cp25_kv_put": [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _P],
+    "cp25_stream_patchify_ld": [_P, _F, _F, _P, _P, _I64, _I64, _P],
+    "cp25_stream_x0_step": [_P, _P, _P, _P, _F, _F, _F, _F, _D, _I, _I64, _P],
     "cp25_unipc_step": [_P, _P, _P, _P, _P, _I64, ctypes.POINTER(UniPCParams), _P],
     "cp25_conv3d": [ctypes.POINTER(ctypes.c_void_p), _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                     _I, _I, _I, _I, _I, _I, _P],
@@ -887,6 +890,72 @@ def trig_x0_step(xs: torch.Tensor, net: torch.Tensor, noise: Optional[torch.Tens
                                int(bool(last)), n_tok, tok0, hw, _stream(xs.device))
     _check("cp25_trig_x0_step", rc)
     return xs
+
+
+def kv_put(qkv: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, *, B: int, k_col0: int, v_col0: int,
+           row0: int) -> None:
+    """cp25_kv_put: the K and V column blocks of the fused QKV rows qkv [n_tok * B, ld] bf16 (row = tok * B + b) into
+    rows [row0, row0 + n_tok) of the caches k_cache / v_cache [B, rows, H, hd] bf16, one launch for both."""
+    lib = load_library()
+    if qkv.dtype != torch.bfloat16 or qkv.dim() != 2 or qkv.stride(1) != 1 or qkv.shape[0] % B:
+        raise ValueError("kv_put: qkv must be bf16 [n_tok * B, ld] rows")
+    for c in (k_cache, v_cache):
+        if c.dtype != torch.bfloat16 or c.dim() != 4 or c.shape[0] != B or c.stride(3) != 1 or \
+                c.stride(2) != c.shape[3] or c.stride() != k_cache.stride() or c.shape != k_cache.shape:
+            raise ValueError("kv_put: caches must be two bf16 [B, rows, H, hd] tensors of one layout, heads contiguous")
+    D = k_cache.shape[2] * k_cache.shape[3]
+    n_tok = qkv.shape[0] // B
+    if max(k_col0, v_col0) + D > qkv.shape[1]:
+        raise ValueError(f"kv_put: columns [{k_col0}, +{D}) / [{v_col0}, +{D}) exceed the {qkv.shape[1]}-wide rows")
+    _check("cp25_kv_put", lib.cp25_kv_put(_ptr(qkv), qkv.stride(0), int(k_col0), int(v_col0), D, _ptr(k_cache),
+                                          _ptr(v_cache), k_cache.stride(0), k_cache.stride(1), k_cache.shape[1], int(B),
+                                          n_tok, int(row0), _stream(qkv.device)))
+
+
+def _check_bf16_rows(name: str, t: torch.Tensor, n_tok: int) -> None:
+    if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.numel() != n_tok * 64:
+        raise ValueError(f"{name} must be contiguous bf16 with {n_tok} x 64 elements, got {t.dtype} {tuple(t.shape)}")
+
+
+def stream_patchify(xs: torch.Tensor, c_in: float, mask: float, pad_mask: Optional[torch.Tensor],
+                    ld: int = 72) -> torch.Tensor:
+    """The streaming student's x_embedder input rows [n_tok, 72] bf16 of one frame (cp25_stream_patchify_ld): channels
+    0..15 = bf16(x * c_in) of the bf16 state xs [n_tok, 64], channel 16 = mask, 17 = pad_mask. c_in / mask: floats
+    holding bf16 values. ld as in patchify (72, or 128: the own GEMM's zero-padded K = 128 operand)."""
+    lib = load_library()
+    n_tok = xs.shape[0]
+    _check_bf16_rows("xs", xs, n_tok)
+    if pad_mask is not None and (pad_mask.dtype != torch.bfloat16 or not pad_mask.is_contiguous()
+                                 or pad_mask.numel() != n_tok * 4):
+        raise ValueError(f"pad_mask must be contiguous bf16 [{n_tok}, 4]")
+    out = torch.empty((n_tok, ld), dtype=torch.bfloat16, device=xs.device)
+    _check("cp25_stream_patchify_ld", lib.cp25_stream_patchify_ld(_ptr(xs), float(c_in), float(mask), _ptr(pad_mask),
+                                                                  _ptr(out), int(ld), n_tok, _stream(xs.device)))
+    return out[:, :72]
+
+
+def stream_x0_step(xs: torch.Tensor, net: torch.Tensor, noise: Optional[torch.Tensor], *, c_skip: float, c_out: float,
+                   cos_next: float, sin_next: float, sigma_data: float, last: bool,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One streaming-student update (cp25_stream_x0_step) of the bf16 state xs [n_tok, 64] from net [n_tok, 1, 64] fp32:
+    x0 = c_skip x + c_out net, then x0 (last) or cos_next x0 / sigma_data + sin_next noise, every op rounded to bf16.
+    The four coefficients are floats holding bf16 values. Returns out (a new bf16 [n_tok, 64] tensor unless given)."""
+    lib = load_library()
+    n_tok = xs.shape[0]
+    _check_bf16_rows("xs", xs, n_tok)
+    _check_patch_rows("net", net, n_tok)
+    if noise is not None:
+        _check_bf16_rows("noise", noise, n_tok)
+    elif not last:
+        raise ValueError("stream_x0_step needs the noise unless last=True")
+    if out is None:
+        out = torch.empty_like(xs)
+    _check_bf16_rows("out", out, n_tok)
+    _check("cp25_stream_x0_step", lib.cp25_stream_x0_step(_ptr(xs), _ptr(net), _ptr(noise), _ptr(out), float(c_skip),
+                                                          float(c_out), float(cos_next), float(sin_next),
+                                                          float(sigma_data), int(bool(last)), n_tok,
+                                                          _stream(xs.device)))
+    return out
 
 
 def unipc_step(x: torch.Tensor, v: torch.Tensor, m0: torch.Tensor, m1: torch.Tensor, last: torch.Tensor,

@@ -176,6 +176,36 @@ class ContextCache:
 
 
 @dataclass
+class KVCache:
+    """Per-block self-attention K / V rings of the per-frame forward (MinimalV1LVGDiT.make_kv_cache / forward_frame)."""
+
+    batch: int
+    cache_frames: int  # past frames a frame attends to
+    hw: int            # tokens per frame
+    k: List[torch.Tensor]  # [B, (cache_frames + 1) * hw, H, hd] bf16 (normed + roped), one per block
+    v: List[torch.Tensor]
+    n_stored: int = 0  # frames 0 .. n_stored - 1 have had their store pass
+
+    @property
+    def slots(self) -> int:
+        return self.cache_frames + 1
+
+    def slot(self, frame: int) -> int:
+        return frame % self.slots
+
+    def n_valid(self, frame: int) -> int:
+        """Slots frame `frame` attends to, always slots 0 .. n_valid - 1: itself and min(frame, cache_frames) before it
+        (fewer than all slots only before the ring first wraps, when the frames sit in slots 0 .. frame)."""
+        return min(frame, self.cache_frames) + 1
+
+    def frames_attended(self, frame: int) -> List[int]:
+        """The frames in slots 0 .. n_valid - 1 while `frame` runs, in slot order."""
+        lo = frame - min(frame, self.cache_frames)
+        by_slot = {self.slot(f): f for f in range(lo, frame + 1)}
+        return [by_slot[s] for s in range(self.n_valid(frame))]
+
+
+@dataclass
 class Geometry:
     T: int   # latent frames (patches along t)
     Hp: int  # patches along h
@@ -670,17 +700,36 @@ class MinimalV1LVGDiT:
                 raise ValueError(f"{A} actions, the net takes {cfg.num_action_per_chunk} per chunk")
             a = a.reshape(Ba, 1, A * dim)
 
-        def mlp(name):  # fc1 and fc2 (+ bias) on the hand-written GEMM, the tanh GELU between them in torch
-            h = self._bias_linear(a.reshape(-1, a.shape[-1]), name + ".fc1")
-            h = F.gelu(h, approximate="tanh")
-            y = self._bias_linear(h, name + ".fc2")
-            return y.view(*a.shape[:-1], -1)
-
-        e_d, e_3d = mlp("action_embedder_B_D"), mlp("action_embedder_B_3D")
+        e_d, e_3d = self._action_mlp("action_embedder_B_D", a), self._action_mlp("action_embedder_B_3D", a)
         if cfg.action_per_latent_frame:
             e_d = torch.cat([torch.zeros_like(e_d[:, :1]), e_d], 1)
             e_3d = torch.cat([torch.zeros_like(e_3d[:, :1]), e_3d], 1)
         if Ba != B:
+            e_d, e_3d = e_d.expand(B, -1, -1), e_3d.expand(B, -1, -1)
+        return e_d, e_3d
+
+    def _action_mlp(self, name: str, a: torch.Tensor) -> torch.Tensor:
+        """One action embedder on a [..., in_features] bf16: fc1 and fc2 (+ bias) on the hand-written GEMM, the tanh
+        GELU between them in torch."""
+        h = self._bias_linear(a.reshape(-1, a.shape[-1]), name + ".fc1")
+        h = F.gelu(h, approximate="tanh")
+        y = self._bias_linear(h, name + ".fc2")
+        return y.view(*a.shape[:-1], -1)
+
+    @torch.no_grad()
+    def frame_action_embedding(self, action: torch.Tensor, B: int):
+        """The streaming student's per-frame action embedding (interactive/networks/dit_action_causal.py:385-404): the
+        frame's actions [B' (1 or B), action_per_latent_frame, action_dim] flattened "b t d -> b 1 (t d)" through both
+        embedder MLPs -> (emb_D [B, 1, D], emb_3D [B, 1, 3D]) bf16. No zero embedding is prepended: a frame without
+        actions (the prefill of the conditioning frame) adds nothing at all (:385)."""
+        cfg = self.cfg
+        a = action.to(device=self.device, dtype=BF16)
+        if a.dim() != 3 or a.shape[1] * a.shape[2] != cfg.action_in_features or a.shape[2] != cfg.action_dim:
+            raise ValueError(f"a frame's actions must be [B, {cfg.action_per_latent_frame}, {cfg.action_dim}], got "
+                             f"{tuple(action.shape)}")
+        a = a.reshape(a.shape[0], 1, -1)
+        e_d, e_3d = self._action_mlp("action_embedder_B_D", a), self._action_mlp("action_embedder_B_3D", a)
+        if a.shape[0] != B:
             e_d, e_3d = e_d.expand(B, -1, -1), e_3d.expand(B, -1, -1)
         return e_d, e_3d
 
@@ -748,13 +797,15 @@ class MinimalV1LVGDiT:
         shift_f, scale_f = f2.chunk(2, dim=-1)
         return mods, shift_f, scale_f
 
-    def _time_modulation_bf16(self, t_B_T: torch.Tensor, action: Optional[torch.Tensor] = None):
+    def _time_modulation_bf16(self, t_B_T: torch.Tensor, action: Optional[torch.Tensor] = None, action_emb=None):
         """time_modulation of a net with use_wan_fp32_strategy=False: the same layers without the fp32 autocast
         (multiview_dit.py:544-548 / multiview_cross_dit.py:823-827, minimal_v4_dit.py:1136-1154 AdaLN, :974-995 final
         layer), i.e. in the net's bf16. Every linear is a bf16 GEMM (bf16 operands, fp32 accumulation, one bf16
         rounding: cp25_gemm_f32 on the bf16 values, rounded), every elementwise op one bf16 torch op: the sinusoid
         rounded to bf16, SiLU on the rounded linear_1 output, TE RMSNorm (fp32 math, one rounding), the AdaLN-LoRA
-        sum `modulation(emb) + lora` of two bf16 tensors. Returns bf16 shift / scale for the final layer."""
+        sum `modulation(emb) + lora` of two bf16 tensors. Returns bf16 shift / scale for the final layer.
+        action_emb (forward_frame): the (emb_D, emb_3D) pair to add instead of action_embedding(action), or False for
+        an action net's frame without actions, which adds none."""
         cfg = self.cfg
         D = cfg.model_channels
         B, T = t_B_T.shape
@@ -765,7 +816,11 @@ class MinimalV1LVGDiT:
         sincos = self._sincos(t_B_T).to(BF16).view(B * T, D)
         h = F.silu(lin(sincos, self.w_t1))
         lora = lin(h, self.w_t2)  # [BT, 3D]
-        if cfg.action_dim:
+        if action_emb is not None:
+            if action_emb is not False:
+                sincos = (sincos.view(B, T, D) + action_emb[0]).reshape(B * T, D)
+                lora = (lora.view(B, T, 3 * D) + action_emb[1]).reshape(B * T, 3 * D)
+        elif cfg.action_dim:
             if action is None:
                 raise ValueError("this action-conditioned net needs `action`")
             e_d, e_3d = self.action_embedding(action, B, T)  # [B, T or 1, *]: broadcast over the frames
@@ -937,6 +992,76 @@ class MinimalV1LVGDiT:
                                       sin, cp, cp_size, prefix=prefix))
         return torch.cat(run_lanes(lanes), dim=1)
 
+    # ---------------------------------------------------------------- streaming: one frame over a K/V cache
+    def make_kv_cache(self, batch: int, cache_frames: int, hw: int) -> "KVCache":
+        """The self-attention K/V ring of every block for the per-frame forward (forward_frame): bf16 K and V buffers
+        of (cache_frames + 1) x hw rows in [B, slot_row, H, hd]; frame t owns slot t mod (cache_frames + 1) and
+        attends to itself and the last min(t, cache_frames) frames. Replaces CausalDITKVCache.make_it_kv_cache /
+        AttenOpWithKV.reset_kv_cache (interactive/networks/dit_causal.py:1087-1101, 1201-1233), whose rolling cache
+        holds cache_frames frames and concatenates the current one to it."""
+        cfg = self.cfg
+        if batch < 1 or cache_frames < 0 or hw < 1:
+            raise ValueError(f"make_kv_cache: batch {batch}, cache_frames {cache_frames}, hw {hw}")
+        shape = (batch, (cache_frames + 1) * hw, cfg.num_heads, cfg.head_dim)
+        k = [torch.zeros(shape, dtype=BF16, device=self.device) for _ in range(cfg.num_blocks)]
+        v = [torch.zeros(shape, dtype=BF16, device=self.device) for _ in range(cfg.num_blocks)]
+        return KVCache(batch=batch, cache_frames=cache_frames, hw=hw, k=k, v=v)
+
+    @torch.no_grad()
+    def forward_frame(self, patch_rows: torch.Tensor, t_B_1: torch.Tensor, ctx: ContextCache, geo: Geometry,
+                      frame_idx: int, action: Optional[torch.Tensor] = None, store: bool = False, *,
+                      cache: "KVCache", rows_k128: bool = False) -> torch.Tensor:
+        """The causal student's forward_seq (interactive/networks/dit_action_causal.py:324-472, 591-638) of latent
+        frame `frame_idx` of the T x Hp x Wp geometry `geo`: patch_rows [hw, Bx, 72] bf16 of that frame alone (Bx = 1
+        shares them across the batch), t_B_1 [B, 1] fp32 already scaled; returns the final layer output [hw, B, 64]
+        fp32. RoPE uses the frame's absolute positions (VideoSeqPos slicing: the frame's rows of the clip's tables);
+        the modulation is this frame's alone. action: the frame's [B' (1 or B), action_per_latent_frame, action_dim]
+        actions, or None (the conditioning frame's prefill: no embedding is added).
+        Each block writes the frame's K / V into its slot of `cache` and attends to the cache's valid slots, the frame
+        itself and the last min(frame_idx, cache_frames) stored frames: the reference's `history ++ current`
+        (AttenOpWithKV.forward, dit_causal.py:1117-1127) in slot order instead of frame order, which a softmax does not
+        see up to rounding. The slot is written on every pass: a denoising pass (store=False) leaves its noisy K / V
+        there, no later frame reads them before the store pass (store=True, on the clean frame) overwrites them, and
+        the slot is none of the history's. store=True also marks the frame as stored: frames are stored in order, and
+        frame t runs only once frames 0 .. t - 1 are."""
+        cfg = self.cfg
+        if cfg.use_wan_fp32_strategy or cfg.n_cameras_emb or cfg.cross_view_attn_map:
+            raise ValueError("forward_frame serves the causal student's net: bf16 conditioning "
+                             "(use_wan_fp32_strategy=False), one view")
+        if self.cp_group is not None:
+            raise ValueError("forward_frame is single-GPU (context-parallel streaming is not built)")
+        if self.attention_precision != "bf16":
+            raise ValueError("forward_frame reads bf16 K / V from the cache: attention_precision must be 'bf16'")
+        B, hw = ctx.B, geo.hw
+        if not 0 <= frame_idx < geo.T:
+            raise ValueError(f"frame {frame_idx} is outside the {geo.T}-frame geometry")
+        if cache.batch != B or cache.hw != hw or len(cache.k) != cfg.num_blocks:
+            raise ValueError(f"the K/V cache (batch {cache.batch}, hw {cache.hw}) does not fit batch {B}, hw {hw}")
+        if cache.n_stored != frame_idx:
+            raise ValueError(f"frame {frame_idx} needs frames 0 .. {frame_idx - 1} stored; the cache holds "
+                             f"{cache.n_stored}")
+        if tuple(t_B_1.shape) != (B, 1) or patch_rows.shape[0] != hw:
+            raise ValueError(f"forward_frame takes t [B, 1] and one frame's {hw} patch rows")
+        one = Geometry(T=1, Hp=geo.Hp, Wp=geo.Wp, tok0=0, n_tok=hw)
+        x_in = self.embed_patches(patch_rows, one, rows_k128=rows_k128)
+        emb = False
+        if action is not None:
+            if not cfg.action_dim:
+                raise ValueError("`action` given to a net without action embedders")
+            emb = self.frame_action_embedding(action, B)
+        mods, shift_f, scale_f = self._time_modulation_bf16(t_B_1.to(self.device), action_emb=emb)
+        full = Geometry(T=geo.T, Hp=geo.Hp, Wp=geo.Wp, tok0=frame_idx * hw, n_tok=hw)
+        cos, sin = self.rope_tables(full)
+        kv = (cache, cache.slot(frame_idx), cache.n_valid(frame_idx))
+        gen = self._blocks(x_in, mods, shift_f, scale_f, ctx, one, cos, sin, None, 1, kv=kv)
+        while True:
+            try:
+                next(gen)
+            except StopIteration as e:
+                if store:
+                    cache.n_stored = frame_idx + 1
+                return e.value
+
     def _view_modulation(self, mods: torch.Tensor, geo: Geometry, view_indices: Optional[torch.Tensor]) -> torch.Tensor:
         """Cross-view nets' AdaLN view embedding (multiview_cross_dit.py:807-813, 355-404): adaln_view_proj(
         adaln_view_embedder(view id)) [V, 9D] (cp25_gemm_f32 with the bias as addend, rounded to bf16: the fp32-autocast
@@ -1022,7 +1147,7 @@ class MinimalV1LVGDiT:
                               pre + "cross_view_attn.output_proj", x, B * D, D, gate1, B, geo, n, lnk, shift, scale)
 
     def _blocks(self, x_in, mods, shift_f, scale_f, ctx: ContextCache, geo: Geometry, cos, sin, cp, cp_size,
-                shared_batch: bool = False, prefix=None, prefix_only: bool = False, cv_nbrs=None):
+                shared_batch: bool = False, prefix=None, prefix_only: bool = False, cv_nbrs=None, kv=None):
         """Generator: issues the 28 blocks + final layer for the batch entries in x_in/mods/ctx on the
         current stream; returns the final layer output [n, B, 64] fp32. Yields (so the caller can
         issue the other lane) right after each self-attention K/V gather is queued (CP > 1), or after
@@ -1034,7 +1159,11 @@ class MinimalV1LVGDiT:
         with batch stride 0 against each entry's own text K/V. Every later sub-layer has per-entry
         inputs. Same values as running both entries (tests/test_dit_gpu.py::test_shared_cfg_block0).
         CP lanes (one entry each) share it the same way: prefix_only=True runs block 0 up to the cross-attention
-        LN-mod for one entry and returns (x, h); each lane then starts from prefix=(x, h)."""
+        LN-mod for one entry and returns (x, h); each lane then starts from prefix=(x, h).
+
+        kv = (KVCache, slot, n_valid) (forward_frame): the tokens are one frame; each block writes its normed + roped K
+        and its V into rows [slot hw, (slot + 1) hw) of its ring cache (cp25_kv_put) and attends to the cache's first
+        n_valid slots, read in place through the cache's strides."""
         cfg = self.cfg
         p = self.sd
         B = ctx.B
@@ -1074,7 +1203,8 @@ class MinimalV1LVGDiT:
                     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 if cp is None or cp_size == 1:
                     q_scale, attn_kw = self._self_attn_mode(i, hd)
-                    kslots = self._k_slots(attn_kw)
+                    # (a K/V cache: the measured key bound would cover this frame's keys only, so the weight bounds)
+                    kslots = self._k_slots(attn_kw) if kv is None else None
                     qkv = self._qkv_k_normed(h, i, n * Bs, Bs, cos, sin, kslots)  # [n*Bs, 3D], k normed + roped
                     if self._q_norm_in_attention(attn_kw):
                         attn_kw = dict(attn_kw, q_norm=dict(weight=p[pre + "self_attn.q_norm.weight"], cos=cos, sin=sin,
@@ -1088,7 +1218,12 @@ class MinimalV1LVGDiT:
                     q = qkv.view(n, Bs, 3 * D)[:, :, :D].view(n, Bs, H, hd).transpose(0, 1)
                     kk = qkv.view(n, Bs, 3 * D)[:, :, D:2 * D].view(n, Bs, H, hd).transpose(0, 1)
                     vv = qkv.view(n, Bs, 3 * D)[:, :, 2 * D:].view(n, Bs, H, hd).transpose(0, 1)
-                    attn_kw = self._fp8_qk(qkv[:, :D], qkv[:, D:2 * D], Bs, H, hd, attn_kw, vv)
+                    if kv is not None:
+                        cache, slot, n_valid = kv
+                        N.kv_put(qkv, cache.k[i], cache.v[i], B=Bs, k_col0=D, v_col0=2 * D, row0=slot * n)
+                        kk, vv = cache.k[i][:, : n_valid * n], cache.v[i][:, : n_valid * n]
+                    else:
+                        attn_kw = self._fp8_qk(qkv[:, :D], qkv[:, D:2 * D], Bs, H, hd, attn_kw, vv)
                     if ev is not None:
                         ev[0].record()
                     if cv_nbrs is not None:

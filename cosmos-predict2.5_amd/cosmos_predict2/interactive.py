@@ -1,0 +1,122 @@
+"""Streaming action-conditioned generation with the causal / self-forcing student on MI355X.
+
+Mirrors the reference's ActionStreamingInference (cosmos_predict2/_src/predict2/interactive/inference/
+action_video2world_streaming.py:90-313): an action sequence is cut into chunks of 12; each chunk conditions on one
+frame (the input frame, then the previous chunk's last decoded frame re-quantised to uint8), generates the chunk's
+T = 4 latent frames one at a time over a K/V cache (model.StreamingRun, a few student steps per frame, no CFG), decodes
+them and contributes the 12 frames after the conditioning one. The noise seed is seed + chunk and the cache is rebuilt per
+chunk.
+
+The text embedding is an input tensor: the reference loads an empty-string embedding file (:130-148).
+Differences: the input frame is resized by this build's resize_input, not mediapy's; the frame arrives
+as an array or an image path, not as a video file whose frame 0 is read.
+"""
+from __future__ import annotations
+
+import os
+from typing import Iterator, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .model import StreamingRun
+from .pipeline import _IMAGE_EXTENSIONS, Video2WorldInference, resize_input
+
+MODEL_NAME = "2B/robot/action-cond/streaming"
+CHUNK_ACTIONS = 12  # :217-227
+
+
+class ActionStreamingInference:
+    """`generate_action_streaming` (the whole video) and `stream_action_chunks` (a generator: each chunk's frames as soon
+    as they are decoded) over one pipeline object (the tokenizer and the streaming student)."""
+
+    def __init__(self, text_embeddings: torch.Tensor, pipe: Optional[Video2WorldInference] = None, **pipe_kwargs):
+        """text_embeddings: [Lctx, dim] or [1, Lctx, dim], what the net's text context takes (the empty-string
+        embedding in the reference). pipe_kwargs go to Video2WorldInference (ckpt_path, tokenizer_path, pixel_path,
+        net_cfg / sampler_cfg overrides, ...)."""
+        self.pipe = pipe or Video2WorldInference(MODEL_NAME, **pipe_kwargs)
+        if self.pipe.model.config.sampler != "dmd2_stream":
+            raise ValueError("ActionStreamingInference needs a streaming ('dmd2_stream') model")
+        emb = text_embeddings
+        if emb.dim() == 2:  # :141-142
+            emb = emb.unsqueeze(0)
+        if emb.dim() != 3 or emb.shape[0] != 1:
+            raise ValueError(f"text embeddings must be [Lctx, dim] or [1, Lctx, dim], got {tuple(text_embeddings.shape)}")
+        self.text_embeddings = emb.to(self.pipe.device, torch.bfloat16)  # :238
+        self._ctx = None  # the net's text context (projection + every block's cross-attention K / V), made once
+
+    # ------------------------------------------------------------------ the input frame
+    def _first_frame(self, first_frame_or_path, resolution_hw) -> torch.Tensor:
+        """uint8 [3, H, W] at the target resolution, on the host."""
+        if isinstance(first_frame_or_path, (str, os.PathLike)):
+            path = os.fspath(first_frame_or_path)
+            if os.path.splitext(path)[1].lower() not in _IMAGE_EXTENSIONS:
+                raise ValueError(f"the conditioning frame must be an image file ({_IMAGE_EXTENSIONS}), got {path}")
+            from PIL import Image
+
+            frame = np.asarray(Image.open(path).convert("RGB")).copy()
+        else:
+            frame = np.asarray(first_frame_or_path)
+        if frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError(f"the conditioning frame must be [H, W, 3], got {frame.shape}")
+        if frame.dtype != np.uint8:
+            frame = np.clip(np.round(frame), 0, 255).astype(np.uint8)  # :209
+        t = torch.from_numpy(np.ascontiguousarray(frame)).permute(2, 0, 1)
+        if resolution_hw is not None and tuple(t.shape[1:]) != tuple(int(v) for v in resolution_hw):
+            t = resize_input(t[None], (int(resolution_hw[0]), int(resolution_hw[1])))[0]
+        H, W = t.shape[1:]
+        if H % 16 or W % 16:
+            raise ValueError(f"resolution {(H, W)}: both sides must be multiples of 16 (8x VAE, 2x2 patches)")
+        return t.contiguous()
+
+    # ------------------------------------------------------------------ generation
+    @torch.no_grad()
+    def stream_action_chunks(self, first_frame_or_path, actions_np: np.ndarray,
+                             resolution_hw: Optional[Tuple[int, int]] = None, num_steps: int = 4, seed: int = 1,
+                             cache_frame_size: int = -1) -> Iterator[torch.Tensor]:
+        """Yields the video piece by piece, each [3, t, H, W] fp32 in [-1, 1] on the host: first the input frame
+        (scaled / 128 - 1, :215), then per chunk of 12 actions its 12 decoded frames, as soon as that chunk is decoded.
+        Concatenated along t they are generate_action_streaming's result."""
+        pipe = self.pipe
+        model, dev = pipe.model, pipe.device
+        ncfg = model.net_cfg
+        actions_np = np.asarray(actions_np)
+        if actions_np.ndim != 2 or actions_np.shape[1] != ncfg.action_dim:
+            raise ValueError(f"actions must be [N, {ncfg.action_dim}], got {actions_np.shape}")
+        if ncfg.action_per_latent_frame != 4:
+            raise ValueError("the chunk loop is written for 4 actions per latent frame (12 actions -> 3 latent frames)")
+        K = len(model.config.selected_sampling_time)
+        n_steps = max(1, min(int(num_steps), K))  # :284-292
+        frame = self._first_frame(first_frame_or_path, resolution_hw)  # uint8 [3, H, W]
+        _, H, W = frame.shape
+        yield frame.float()[:, None] / 128 - 1  # :215
+        on_device = pipe.pixel_path == "device"
+        if on_device:
+            frame = frame.to(dev)
+        T_lat = model.tokenizer.get_latent_num_frames(1 + CHUNK_ACTIONS)
+        for ar_idx in range(actions_np.shape[0] // CHUNK_ACTIONS):
+            # the chunk's 13-frame video is the conditioning frame + 12 zero frames (:219-222); the causal VAE's latent
+            # frame 0 depends on pixel frame 0 alone, and the loop reads no other frame of x0 (encode_conditioning)
+            gt = model.encode_conditioning(frame[None, :, None], 1, T_lat)
+            a = torch.from_numpy(np.ascontiguousarray(actions_np[ar_idx * CHUNK_ACTIONS:(ar_idx + 1) * CHUNK_ACTIONS]))
+            a = a.float().unsqueeze(0).to(dev, torch.bfloat16)  # :168, :177
+            if self._ctx is None:  # the same text for every chunk (the reference re-projects it in every forward)
+                self._ctx = model.net.prepare_context(self.text_embeddings)
+            run = StreamingRun(model, gt, self._ctx, a, seed=seed + ar_idx, n_steps=n_steps,
+                               cache_frame_size=cache_frame_size)  # a fresh cache per chunk (:475-480)
+            while not run.done:
+                run.next_frame()
+            video = model.decode(run.latents()).clip(min=-1, max=1)  # bf16, as the latents (:302-303)
+            # the next chunk's conditioning frame, re-quantised in the video's bf16 (:310)
+            frame = ((1.0 + video[0:1, :, -1]) / 2 * 255.0).to(torch.uint8)[0]
+            if not on_device:
+                frame = frame.cpu()
+            yield video[0, :, 1:].float().cpu()  # :307
+
+    @torch.no_grad()
+    def generate_action_streaming(self, first_frame_or_path, actions_np: np.ndarray,
+                                  resolution_hw: Optional[Tuple[int, int]] = None, num_steps: int = 4, seed: int = 1,
+                                  cache_frame_size: int = -1) -> torch.Tensor:
+        """-> video [3, 1 + 12 (len(actions) // 12), H, W] fp32 in [-1, 1] (action_video2world_streaming.py:183-313)."""
+        return torch.cat(list(self.stream_action_chunks(first_frame_or_path, actions_np, resolution_hw, num_steps, seed,
+                                                        cache_frame_size)), dim=1)

@@ -16,6 +16,9 @@ A model whose SamplerConfig.sampler is "dmd2" samples with the DMD2-distilled fe
 (DistilledSamplingRun; reference: distill/models/video2world_model_distill_dmd2.py:421-492 and denoise_edm,
 video2world_model_rectified_flow.py:214-346): TrigFlow preconditioning + patchify (HIP) -> one DiT forward at B = 1
 -> x0 reconstruction + re-noising (HIP), four times, with no CFG and no solver history.
+
+A "dmd2_stream" model is the causal / self-forcing action student, generated one latent frame at a time over a K/V
+cache (StreamingRun, generate_streaming_video; reference: interactive/models/action_video2world_self_forcing.py:170-577).
 """
 from __future__ import annotations
 
@@ -28,7 +31,7 @@ import torch
 from . import _native as N
 from . import context_parallel as cpu
 from . import trigflow
-from .dit import Geometry, MinimalV1LVGDiT
+from .dit import ContextCache, Geometry, MinimalV1LVGDiT
 from .net_config import DiTConfig, SamplerConfig
 from .scheduler import FlowUniPCMultistepScheduler
 
@@ -127,8 +130,12 @@ class Video2WorldModelRectifiedFlow:
             return DistilledSamplingRun(self, gt, ctx_cond, state_shape=state_shape,
                                         num_conditional_frames=num_conditional_frames, seed=seed,
                                         num_steps=num_steps, net_fn=net_fn, init_noise=init_noise)
+        if self.config.sampler == "dmd2_stream":
+            raise ValueError("the streaming (dmd2_stream) student generates frame by frame: generate_streaming_video / "
+                             "StreamingRun, not the chunk sampler")
         if self.config.sampler != "unipc":
-            raise ValueError(f"unknown SamplerConfig.sampler {self.config.sampler!r} ('unipc' or 'dmd2')")
+            raise ValueError(f"unknown SamplerConfig.sampler {self.config.sampler!r} ('unipc', 'dmd2' or "
+                             "'dmd2_stream')")
         if init_noise is not None:
             raise ValueError("`init_noise` is the distilled (dmd2) sampler's argument")
         return SamplingRun(self, gt, ctx_cond, ctx_uncond, state_shape=state_shape,
@@ -156,6 +163,23 @@ class Video2WorldModelRectifiedFlow:
             i = run.step()
             if progress is not None:
                 progress(i, run.num_evals)
+        return run.latents()
+
+    @torch.no_grad()
+    def generate_streaming_video(self, gt: torch.Tensor, ctx: torch.Tensor, actions: torch.Tensor, *,
+                                 init_noise: Optional[torch.Tensor] = None, seed: int = 0, n_steps: int = 4,
+                                 cache_frame_size: Optional[int] = None, net_fn=None) -> torch.Tensor:
+        """The streaming action student's clip (StreamingRun): gt [1, C, T, H, W] whose frame 0 conditions the clip, ctx
+        the text embedding [1, Lctx, proj_in], actions [1, (T - 1) * action_per_latent_frame, action_dim]; noise from
+        init_noise [1, C, T, H, W] or arch_invariant_rand(seed); cache_frame_size None = the config's. Returns the
+        latents [1, C, T, H, W] bf16 (interactive/models/action_video2world_self_forcing.py:449-577)."""
+        if self.config.sampler != "dmd2_stream":
+            raise ValueError(f"generate_streaming_video needs a 'dmd2_stream' sampler config, got "
+                             f"{self.config.sampler!r}")
+        run = StreamingRun(self, gt, ctx, actions, seed=seed, n_steps=n_steps, cache_frame_size=cache_frame_size,
+                           net_fn=net_fn, init_noise=init_noise)
+        while not run.done:
+            run.next_frame()
         return run.latents()
 
     @torch.no_grad()
@@ -479,3 +503,109 @@ class DistilledSamplingRun(_TokenState):
         del net_out
         self.i += 1
         return self.i - 1
+
+
+class StreamingRun:
+    """The causal / self-forcing action student, one latent frame at a time over a K/V cache (config.sampler ==
+    "dmd2_stream"): ActionVideo2WorldModelRFSelfForcingDMD2.generate_streaming_video / generate_next_frame around
+    denoise_edm_seq (interactive/models/action_video2world_self_forcing.py:449-577, 383-447, 170-227).
+
+        prefill(): the start_idx = 1 conditioning frame at t = 0, stored in the cache, no action (:499-527)
+        next_frame(): n_steps evaluations at selected_sampling_time[:n_steps] from the frame's noise, not stored
+                      (:416-444), then one store pass at t = 0 on the predicted frame with the frame's actions (:546-575)
+    One evaluation is stream_patchify (HIP: x * c_in in bf16, the patch rows) -> forward_frame at B = 1 over the cache
+    -> stream_x0_step (HIP: x0 = c_skip x + c_out net and the re-noising, bf16 op by op). The state, the noise and the
+    latents are bf16, as the reference casts them to the net dtype (:457, inference/action_video2world_streaming.py:256);
+    the per-evaluation scalars are a few bf16 values made on the host (trigflow.stream_scaling / stream_renoise).
+    The condition mask is all zeros in this loop (:514-516, :558-560), so t_cond never shows; the arithmetic that would
+    apply it is kept (stream_scaling).
+    net_fn(rows [hw, 1, 72] bf16, t_B_1 [1, 1] fp32, geo, frame_idx, action [1, per, dim] | None, store) -> [hw, 1, 64]
+    fp32 replaces forward_frame (tests only)."""
+
+    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt: torch.Tensor, ctx, actions: torch.Tensor, *,
+                 seed: int = 0, n_steps: int = 4, cache_frame_size: Optional[int] = None, net_fn=None,
+                 init_noise: Optional[torch.Tensor] = None):
+        cfg, ncfg, dev = model.config, model.net_cfg, model.device
+        times = [float(t) for t in cfg.selected_sampling_time]
+        if not 1 <= n_steps <= len(times):  # :453-455
+            raise ValueError(f"n_steps must be in 1 .. {len(times)} (the student schedule), got {n_steps}")
+        if gt.dim() != 5 or gt.shape[0] != 1:
+            raise ValueError(f"gt must be the [1, C, T, H, W] conditioning latent, got {tuple(gt.shape)}")
+        _, C, T, H, W = gt.shape
+        per = ncfg.action_per_latent_frame
+        if not per or actions.dim() != 3 or actions.shape[1] != (T - 1) * per or actions.shape[2] != ncfg.action_dim:
+            raise ValueError(f"actions must be [1, {(T - 1) * max(per, 1)}, {ncfg.action_dim}] for {T} latent frames "
+                             f"of a per-latent-frame action net, got {tuple(actions.shape)}")
+        self.model, self.net_fn, self.n_steps = model, net_fn, n_steps
+        self.state_shape = (C, T, H, W)
+        self.geo = Geometry(T=T, Hp=H // 2, Wp=W // 2, tok0=0, n_tok=T * (H // 2) * (W // 2))
+        hw = self.geo.hw
+        if init_noise is None:
+            init_noise = arch_invariant_rand((1, C, T, H, W), torch.float32, dev, seed)
+        elif tuple(init_noise.shape) != (1, C, T, H, W):
+            raise ValueError(f"init_noise {tuple(init_noise.shape)} is not the state shape {(1, C, T, H, W)}")
+        bf = torch.bfloat16
+        self.noise = to_patch_layout(init_noise[0].to(dev, bf)).view(T, hw, 64)  # init_noise.to(**tensor_kwargs)
+        self.out = torch.zeros((T, hw, 64), dtype=bf, device=dev)  # output_latents, patch layout
+        self.out[0] = to_patch_layout(gt[0, :, :1].to(dev, bf))
+        self.actions = actions.to(dev).view(actions.shape[0], T - 1, per, ncfg.action_dim)
+        F = cfg.cache_frame_size if cache_frame_size is None else cache_frame_size
+        if F == 0 or F < -1:
+            raise ValueError(f"cache_frame_size must be -1 (the whole clip) or positive, got {F}")
+        # a frame attends to at most T - 1 earlier ones, so that many slots serve -1 (the reference sizes T) and above
+        self.cache_frames = T - 1 if F == -1 else min(F, T - 1)
+        self.cache = None
+        self.ctx = None
+        if net_fn is None:
+            # the text context's per-block K / V: a ContextCache made once by the caller, or made here
+            self.ctx = ctx if isinstance(ctx, ContextCache) else model.net.prepare_context(ctx)
+            self.cache = model.net.make_kv_cache(1, self.cache_frames, hw)
+        sc = lambda t: trigflow.stream_scaling(t, 0.0, cfg.trig_scaling, cfg.sigma_data, cfg.sigma_conditional)  # noqa: E731
+        self.sigma_data = float(cfg.sigma_data)
+        self.steps = []
+        for s in range(n_steps):
+            c_skip, c_out, c_in, c_noise = sc(times[s])
+            last = s == n_steps - 1
+            cos_n, sin_n = (0.0, 0.0) if last else trigflow.stream_renoise(times[s + 1])
+            self.steps.append(dict(c_skip=c_skip, c_out=c_out, c_in=c_in, cos_next=cos_n, sin_next=sin_n, last=last,
+                                   t_B_1=trigflow.net_timesteps(c_noise, ncfg.timestep_scale).to(dev)))
+        _, _, c_in0, c_noise0 = sc(0.0)
+        self.store_step = dict(c_in=c_in0, t_B_1=trigflow.net_timesteps(c_noise0, ncfg.timestep_scale).to(dev))
+        self.frame = 0  # the next frame to run: 0 = the prefill
+
+    @property
+    def done(self) -> bool:
+        return self.frame >= self.geo.T
+
+    def _net(self, x: torch.Tensor, step: dict, frame: int, action, store: bool) -> torch.Tensor:
+        rows = N.stream_patchify(x, step["c_in"], 0.0, None, ld=128).view(self.geo.hw, 1, -1)
+        if self.net_fn is not None:
+            return self.net_fn(rows, step["t_B_1"], self.geo, frame, action, store)
+        return self.model.net.forward_frame(rows, step["t_B_1"], self.ctx, self.geo, frame, action, store,
+                                            cache=self.cache, rows_k128=True)
+
+    @torch.no_grad()
+    def next_frame(self) -> int:
+        """Run the next frame (the first call: the conditioning frame's prefill); returns its index."""
+        if self.done:
+            raise RuntimeError("every frame of the clip has been generated")
+        f = self.frame
+        if f == 0:
+            self._net(self.out[0], self.store_step, 0, None, True)
+        else:
+            action = self.actions[:, f - 1]
+            x = self.noise[f]
+            for s in self.steps:
+                net_out = self._net(x, s, f, action, False)
+                x = N.stream_x0_step(x, net_out.contiguous(), self.noise[f], c_skip=s["c_skip"], c_out=s["c_out"],
+                                     cos_next=s["cos_next"], sin_next=s["sin_next"], sigma_data=self.sigma_data,
+                                     last=s["last"], out=self.out[f] if s["last"] else None)
+            self._net(self.out[f], self.store_step, f, action, True)
+        self.frame += 1
+        return f
+
+    @torch.no_grad()
+    def latents(self) -> torch.Tensor:
+        """output_latents [1, C, T, H, W] bf16 (frames not yet generated are zero, as the reference initialises them)."""
+        _, T, H, W = self.state_shape
+        return from_patch_layout(self.out.view(-1, 64), T, H, W).unsqueeze(0)

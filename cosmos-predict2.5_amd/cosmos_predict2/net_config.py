@@ -117,6 +117,11 @@ class SamplerConfig:
     sigma_data: float = 1.0
     sigma_conditional: float = 1e-4  # noise level of the conditioning frames: t_cond = atan(sigma_conditional / sigma_data)
     change_time_embed: bool = False  # the student's c_noise(t) = t (denoise_edm :268-270)
+    # "dmd2_stream": the causal / self-forcing action student, one latent frame at a time over a K/V cache
+    # (model.StreamingRun; interactive/models/action_video2world_self_forcing.py:449-577). It reads the TrigFlow fields
+    # above and cache_frame_size: the number of past frames a frame attends to (-1: all of the clip's; the reference's
+    # generate_streaming_video argument, --cache_frame_size of interactive/inference/action_video2world_streaming.py:74-79)
+    cache_frame_size: int = -1
 
 
 DIT_2B = DiTConfig()
@@ -170,6 +175,30 @@ SAMPLER_2B_DISTILLED = SamplerConfig(sampler="dmd2",
                                      trig_scaling="rectified_flow", sigma_data=1.0, sigma_conditional=0.0001,
                                      state_t=24, denoise_replace_gt_frames=True, resolution="720")
 
+# Causal / self-forcing action student, streamed frame by frame over a K/V cache (paths under
+# cosmos_predict2/_src/predict2/interactive/). Net: ACTION_CAUSAL_KVCACHE_COSMOS_V1_2B_NET_MININET (configs/net.py:122-130:
+# ActionChunkCausalDITwithConditionalMaskKVCache, model_channels 2048, 28 blocks, 16 heads, no per-block absolute
+# pos-emb, rope t 1.0) over BASE_NET_KWARGS (:30-50: max_img 240 x 240, 128 frames, 16 in / out channels, patch 2 / 1,
+# padding-mask channel, AdaLN-LoRA 256, rope h / w 1.0), with the experiment's net=dict(...) on top
+# (configs/experiment/exp_action_self_forcing.py:92-105: action_dim 29, temporal_compression_ratio 4 = actions per
+# latent frame, rope h / w 3.0, t 24 / 24, fps modulation off, crossattn projection 100352 -> 1024). Neither sets
+# timestep_scale nor use_wan_fp32_strategy, so the class defaults hold: 1.0 (networks/dit_action_causal.py:71) and False
+# (networks/dit_causal.py:614); mlp_ratio 4.0 (:589); the embedder MLPs' hidden width 4 * model_channels
+# (dit_action_causal.py:83-84). The +1 condition-mask input channel is dit_action_causal.py:549-553.
+# Sampler (exp_action_self_forcing.py:147, 160-163): scaling "rectified_flow", the four student times, sigma_conditional
+# 1e-4, sigma_data 1.0, state_t = 1 + 12 // 4 = 4; resolution "720" (:145) is the training bucket, the streaming script
+# takes H, W from its --resolution argument (inference/action_video2world_streaming.py:198-202).
+# Where CausalDIT / CausalBlock differ from MiniTrainDIT / Block is listed in DESIGN.md §6e (state-dict names are the
+# same; the image-context cross-attention and the per-block absolute pos-emb are not built by this net).
+DIT_2B_ACTION_STREAMING = DIT_2B.replace(action_dim=29, action_per_latent_frame=4, timestep_scale=1.0,
+                                         use_wan_fp32_strategy=False, rope_h_extrapolation_ratio=3.0,
+                                         rope_w_extrapolation_ratio=3.0, rope_t_extrapolation_ratio=1.0)
+SAMPLER_ACTION_STREAMING = SamplerConfig(sampler="dmd2_stream",
+                                         selected_sampling_time=(math.pi / 2, math.atan(15), math.atan(5),
+                                                                 math.atan(5 / 3)),
+                                         trig_scaling="rectified_flow", sigma_data=1.0, sigma_conditional=0.0001,
+                                         state_t=4, resolution="720", cache_frame_size=-1)
+
 # model name (cosmos_predict2/config.py ModelKey.name) -> (net, sampler)
 MODELS = {
     "2B/post-trained": (DIT_2B, SAMPLER_2B_POST_TRAINED),
@@ -182,6 +211,8 @@ MODELS = {
     # the reference ships the distillation recipe and the student's inference loop but no checkpoint key for a
     # distilled model (checkpoint_db.py has none): this entry serves a student distilled with that recipe
     "2B/distilled": (DIT_2B_DISTILLED, SAMPLER_2B_DISTILLED),
+    # likewise no checkpoint key: the streaming action student trained with interactive/'s self-forcing recipe
+    "2B/robot/action-cond/streaming": (DIT_2B_ACTION_STREAMING, SAMPLER_ACTION_STREAMING),
 }
 
 # Subset of VIDEO_RES_SIZE_INFO (cosmos_predict2/_src/predict2/datasets/utils.py:44-67); the model's

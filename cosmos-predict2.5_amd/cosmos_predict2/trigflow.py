@@ -9,6 +9,10 @@ Everything here is a handful of float64 values per latent frame, computed with C
 the per-element work is cp25_trig_patchify_ld / cp25_trig_x0_step. Deviation: the reference evaluates
 atan / cos / sin / tan / log of these tables on CUDA float64 tensors and this build on the host, so agreement in the
 last ulp of those functions is not pinned.
+
+stream_scaling / stream_renoise are the same tables for the streaming causal student (interactive/models/
+action_video2world_self_forcing.py:185-203, 441-443), whose times and coefficients are bf16 tensors: a few bf16 values
+per evaluation, made with CPU torch bf16 ops; the per-element work is cp25_stream_patchify_ld / cp25_stream_x0_step.
 """
 from __future__ import annotations
 
@@ -65,6 +69,32 @@ def step_times(selected_sampling_time: Sequence[float], num_steps: int) -> List[
 def renoise_scalars(t_next: float) -> Tuple[float, float, bool]:
     """(cos t_next, sin t_next, last) of one step (dmd2 :487-488, Python's math as there)."""
     return math.cos(t_next), math.sin(t_next), not (t_next > LAST_STEP_EPS)
+
+
+BF16 = torch.bfloat16
+
+
+def stream_scaling(t: float, frame_mask: float, scaling: str, sigma_data: float,
+                   sigma_conditional: float) -> Tuple[float, float, float, torch.Tensor]:
+    """The streaming student's coefficients of one evaluation at TrigFlow time t (denoise_edm_seq,
+    interactive/models/action_video2world_self_forcing.py:185-203): (c_skip, c_out, c_in) as Python floats holding bf16
+    values, and c_noise as a bf16 [1] tensor for net_timesteps. There the time is a bf16 tensor (torch.full(...,
+    dtype=bfloat16), :420, or zeros in the net dtype, :524), the mask's mean is cast to it, and
+    `t_cond * mask + time * (1 - mask)` is four bf16 ops, written out here though this loop's mask is always 0; the
+    sCM wrappers compute in float64 and return the coefficients cast back to the time's bf16
+    (modules/denoiser_scaling.py:33-34, 43, 51-52, 67)."""
+    time = torch.full((1,), float(t), dtype=BF16)
+    m = torch.full((1,), float(frame_mask), dtype=BF16)
+    t_cond = torch.atan(torch.ones_like(time) * (sigma_conditional / sigma_data))
+    time = t_cond * m + time * (1 - m)
+    c_skip, c_out, c_in, c_noise = (c.to(BF16) for c in trig_scaling(time.to(F64), scaling, sigma_data))
+    return float(c_skip), float(c_out), float(c_in), c_noise
+
+
+def stream_renoise(t_next: float) -> Tuple[float, float]:
+    """(cos, sin) of the 0-dim bf16 tensor torch.tensor(t_next, dtype=bfloat16) (:441-443), each a bf16 value."""
+    tn = torch.tensor(float(t_next), dtype=BF16)
+    return float(torch.cos(tn)), float(torch.sin(tn))
 
 
 def net_timesteps(c_noise: torch.Tensor, timestep_scale: float) -> torch.Tensor:

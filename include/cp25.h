@@ -425,6 +425,40 @@ int cp25_trig_x0_step(float* xs, const float* net, const float* noise, const flo
                       const double* c_skip, const double* c_out, int replace_gt, double sigma_data, double cos_next,
                       double sin_next, int last, int64_t n_tok, int64_t tok0, int64_t hw, hipStream_t stream);
 
+/* ---------------------------------------------------------------- streaming causal action student (stream_ops.hip)
+ * The KV-cached per-frame student (interactive/models/action_video2world_self_forcing.py:170-227, 383-577 around
+ * interactive/networks/dit_causal.py:1062-1159). Its arithmetic is bf16, op by op: every torch op there is one
+ * operation on bf16 tensors, evaluated in fp32 and rounded once to bf16 (NaN -> 0x7FC0, as c10::BFloat16 rounds). The
+ * state, the noise and the outputs are bf16 in the patch layout above, one latent frame, one batch entry. The scalar
+ * coefficients are bf16 tensors in the reference and are passed as floats that hold bf16 values exactly; -22 for a
+ * float that does not, for a misaligned (16 B) pointer or a bad size.
+ *
+ * cp25_kv_put: rows r = tok * B + b of the fused QKV buffer qkv [n_tok * B, ld] bf16: columns [k_col0, k_col0 + D) ->
+ * k_cache[b, row0 + tok, :], [v_col0, v_col0 + D) -> v_cache[b, row0 + tok, :], caches [B, cache_rows, D] with batch /
+ * row strides cache_sb / cache_sr (elements), as 16-byte moves, one launch for both. D, ld, the column offsets and the
+ * strides are multiples of 8; row0 + n_tok <= cache_rows. Replaces AttenOpWithKV's `k_cache[:, s:e] = k` pair. */
+int cp25_kv_put(const void* qkv, int64_t ld, int64_t k_col0, int64_t v_col0, int64_t D, void* k_cache, void* v_cache,
+                int64_t cache_sb, int64_t cache_sr, int64_t cache_rows, int B, int64_t n_tok, int64_t row0,
+                hipStream_t stream);
+
+/* cp25_patchify_ld's rows of one frame from the bf16 state xs [n_tok, 64]: channels 0..15 = bf16(x * c_in), channel 16
+ * = mask, channel 17 = pad_mask ([n_tok, 4] bf16, NULL = 0), columns 72 .. 127 zeroed when out_ld = 128. out_ld is 72
+ * or 128 (-95 otherwise). Replaces denoise_edm_seq :206, :211 and forward_seq's mask concatenation. */
+int cp25_stream_patchify_ld(const void* xs, float c_in, float mask, const void* pad_mask, void* out, int64_t out_ld,
+                            int64_t n_tok, hipStream_t stream);
+
+/* From the bf16 state xs [n_tok, 64] and the net output net [n_tok, 1, 64] fp32 (rounded to bf16 first, the
+ * reference's `.to(dtype=x.dtype)`), into out [n_tok, 64] bf16 (may be xs):
+ *   x0 = bf16(bf16(c_skip * x) + bf16(c_out * net))                                                  (:226)
+ *   last != 0: out = x0
+ *   last == 0: out = bf16(bf16(bf16(cos_next * x0) * (1.0f / float(sigma_data))) + bf16(sin_next * noise))  (:442-444)
+ * cos_next / sin_next: cos / sin of the 0-dim bf16 tensor t_next, already rounded to bf16. `/ self.sigma_data` divides
+ * a device tensor by a Python float, which PyTorch evaluates as a multiplication by the fp32 reciprocal. noise
+ * [n_tok, 64] bf16, may be NULL when last != 0. */
+int cp25_stream_x0_step(const void* xs, const float* net, const void* noise, void* out, float c_skip, float c_out,
+                        float cos_next, float sin_next, double sigma_data, int last, int64_t n_tok,
+                        hipStream_t stream);
+
 /* ---------------------------------------------------------------- UniPC sampler update
  * Host-computed fp32 coefficients of one FlowUniPCMultistepScheduler.step. */
 typedef struct cp25_unipc_params {
