@@ -88,6 +88,8 @@ SIGNATURES = {
     "cp25_attn_tail_workspace_bytes": [_I, _I, _I, _I],
     "cp25_attn_kernel": [_I, _F, _F, _F, _I, _I],
     "cp25_attn_plan": [_I, _I, _I, _I, _I],
+    "cp25_attn_na3d": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, c_int64_p, c_int64_p, c_int64_p, c_int64_p, _P, _P, _I, _I,
+                       ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _F, _I, _P],
     "cp25_ln_mod": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _P, _I64, _I, _I, _I64, _I64, _F, _P],
     "cp25_ln_mod_fp8": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I, _I, _I64, _I64, _F, _P],
     "cp25_final_ln_mod": [_P, _P, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _I, _I, _I64, _I64, _F, _P],
@@ -390,6 +392,50 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[to
         scale, qb, kb, int(n_split), _ptr(ws), ws_bytes, _stream(q.device),
     )
     _check("cp25_attn_fwd_bounded", rc)
+    return out
+
+
+NA_TILE_ROWS = 128  # query rows per plan tile of attn_na3d (attn_na.hip kNaRows)
+
+
+def attn_na3d(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, plan, out: Optional[torch.Tensor] = None,
+              softmax_scale: Optional[float] = None, prescaled: bool = False) -> torch.Tensor:
+    """3D neighborhood attention (cp25_attn_na3d) of q / k / v [B, L, H, 128] bf16 (any strides with a contiguous
+    head dim) over the token grid plan.grid = (T, H, W), L = T H W: each query attends the key box of its plan tile
+    (sparse_attn.build_plan: plan.q_tok int32 [n_tiles, 128], plan.box int32 [n_tiles, 4] device tables, plan.window /
+    plan.dilation per axis). Returns [B, L, H, 128] bf16. prescaled=True: q rows already carry scale * log2(e)
+    (head_rmsnorm_rope(out_scale=...)); softmax_scale is then unused."""
+    lib = load_library()
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise ValueError("attn_na3d expects bf16 q/k/v")
+    if q.dim() != 4 or tuple(k.shape) != tuple(q.shape) or tuple(v.shape) != tuple(q.shape):
+        raise ValueError(f"attn_na3d: q/k/v [B, L, H, D] of one shape expected, got q{tuple(q.shape)} "
+                         f"k{tuple(k.shape)} v{tuple(v.shape)}")
+    B, L, H, D = q.shape
+    T, Hg, Wg = (int(x) for x in plan.grid)
+    if L != T * Hg * Wg:
+        raise ValueError(f"attn_na3d: {L} tokens do not fill the plan's grid {tuple(plan.grid)}")
+    for t in (q, k, v):
+        if t.stride(3) != 1:
+            raise ValueError("head dim must be contiguous")
+    q_tok, box = plan.q_tok, plan.box
+    if q_tok.dtype != torch.int32 or box.dtype != torch.int32 or not q_tok.is_contiguous() or not box.is_contiguous() \
+            or q_tok.dim() != 2 or q_tok.shape[1] != NA_TILE_ROWS or tuple(box.shape) != (q_tok.shape[0], 4) \
+            or q_tok.device != q.device or box.device != q.device:
+        raise ValueError(f"attn_na3d: plan tables must be contiguous int32 q_tok [n, {NA_TILE_ROWS}] and box [n, 4] "
+                         "on q's device")
+    if out is None:
+        out = torch.empty((B, L, H, D), dtype=torch.bfloat16, device=q.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (B, L, H, D) or out.stride(3) != 1:
+        raise ValueError("attn_na3d: out must be bf16 [B, L, H, D] with a contiguous head dim")
+    scale = float(D) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    strides = [_i64x3((t.stride(0), t.stride(1), t.stride(2))) for t in (q, k, v, out)]
+    win = (ctypes.c_int * 3)(*[int(x) for x in plan.window])
+    dil = (ctypes.c_int * 3)(*[int(x) for x in plan.dilation])
+    rc = lib.cp25_attn_na3d(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, H, T, Hg, Wg, D, *strides, _ptr(q_tok), _ptr(box),
+                            int(q_tok.shape[0]), NA_TILE_ROWS, win, dil, scale, int(bool(prescaled)),
+                            _stream(q.device))
+    _check("cp25_attn_na3d", rc)
     return out
 
 

@@ -26,6 +26,7 @@ import torch.nn.functional as F
 from . import _native as N
 from .context_parallel import all_gather_into_async, kv_chunk_views, run_lanes
 from .net_config import DiTConfig
+from .sparse_attn import PlanCache, sparse_block_params
 
 BF16 = torch.bfloat16
 F32 = torch.float32
@@ -321,6 +322,14 @@ class MinimalV1LVGDiT:
         # the Q fragments as they load, bit-identical, no separate pass over q in HBM); prescaled bf16 form only
         self.fused_q_norm = True
         self._x_embed_w128 = None  # the x_embedder weight zero-padded to K = 128 (embed_patches' own-GEMM path)
+        # sparse blocks (cfg.n_dense_blocks / natten_parameters): per-block NattenParams, None = dense; their
+        # neighborhood plans (sparse_attn.build_plan) are cached per (patch grid, parameters)
+        self.sparse_params = sparse_block_params(cfg.num_blocks, cfg.n_dense_blocks, cfg.natten_parameters or None)
+        self.has_sparse_blocks = any(sp is not None for sp in self.sparse_params)
+        if self.has_sparse_blocks and (cfg.n_cameras_emb or cfg.cross_view_attn_map):
+            raise NotImplementedError("sparse (neighborhood) self-attention is not built for multi-view / cross-view "
+                                      "nets")
+        self._na_plans = PlanCache(self.device)
 
     def set_linear_precision(self, precision: str) -> None:
         """"bf16" (default, the reference's arithmetic) or "fp8": the 28 blocks' q/k/v, output, cross-q,
@@ -345,6 +354,8 @@ class MinimalV1LVGDiT:
         tests/test_parity_depth_gpu.py::test_full_depth_2b_forward_fp8_modes."""
         if precision not in ("bf16", "fp8qk", "fp8"):
             raise ValueError(f"attention precision must be 'bf16', 'fp8qk' or 'fp8', got {precision!r}")
+        if precision != "bf16" and self.has_sparse_blocks:
+            raise NotImplementedError("fp8 attention is not built for a net with sparse (neighborhood) blocks")
         self.attention_precision = precision
 
     def _fp8_qk(self, q_cols: torch.Tensor, k_cols: torch.Tensor, B: int, H: int, hd: int, attn_kw: dict,
@@ -577,10 +588,38 @@ class MinimalV1LVGDiT:
             self.cvattn_bounds = [(nb(p[f"blocks.{i}.cross_view_attn.q_norm.weight"]),
                                    nb(p[f"blocks.{i}.cross_view_attn.k_norm.weight"])) for i in range(cfg.num_blocks)]
 
+    def _sparse_plan(self, i: int, geo: "Geometry", cp_size: int = 1, kv=None, cv_nbrs=None):
+        """The neighborhood plan of block i's self-attention over geo's patch grid; None for a dense block and for a
+        one-frame input (T == 1 runs dense attention, neighborhood_attn.py:226-228). Sparse blocks combined with
+        context parallelism, a K/V cache, fp8 attention or views raise: none of these is built."""
+        sp = self.sparse_params[i]
+        if sp is None:
+            return None
+        if cp_size > 1:
+            raise NotImplementedError("sparse (neighborhood) self-attention under context parallelism (cp_size > 1) is "
+                                      "not built")
+        if kv is not None:
+            raise NotImplementedError("sparse (neighborhood) self-attention over a K/V cache (forward_frame) is not "
+                                      "built")
+        if self.attention_precision != "bf16":
+            raise NotImplementedError("fp8 attention is not built for sparse (neighborhood) blocks")
+        if cv_nbrs is not None or geo.n_views > 1 or geo.frames is not None:
+            raise NotImplementedError("sparse (neighborhood) self-attention is not built for multi-view inputs")
+        if geo.tok0 != 0 or geo.n_tok != geo.L:
+            raise NotImplementedError("sparse (neighborhood) self-attention needs the whole token grid on one rank")
+        if geo.T == 1:
+            return None
+        return self._na_plans.get((geo.T, geo.Hp, geo.Wp), sp)
+
     def attention_kernels(self, L: int) -> Dict[str, str]:
-        """The attention kernel forms block 0 launches at L tokens (self) and against the text context (cross)."""
+        """The attention kernel forms block 0 launches at L tokens (self) and against the text context (cross); a net
+        with sparse blocks also names their kernel ("sparse") and lists them ("sparse_blocks")."""
         hd = self.cfg.head_dim
         out = {}
+        if self.has_sparse_blocks:
+            pre = self._self_attn_mode(0, hd)[1].get("prescaled", False)
+            out["sparse"] = "attn_na3d<box, %sonline max>" % ("prescaled, " if pre else "")
+            out["sparse_blocks"] = ",".join(str(i) for i, sp in enumerate(self.sparse_params) if sp is not None)
         for name, bounds, lk in (("self", self.attn_bounds[0], L), ("cross", self.xattn_bounds[0], 512)):
             _, kw = self._attn_mode(bounds, hd)
             fp8 = 0
@@ -1032,6 +1071,9 @@ class MinimalV1LVGDiT:
             raise ValueError("forward_frame is single-GPU (context-parallel streaming is not built)")
         if self.attention_precision != "bf16":
             raise ValueError("forward_frame reads bf16 K / V from the cache: attention_precision must be 'bf16'")
+        if self.has_sparse_blocks:
+            raise NotImplementedError("forward_frame (K/V cache) is not built for a net with sparse (neighborhood) "
+                                      "blocks")
         B, hw = ctx.B, geo.hw
         if not 0 <= frame_idx < geo.T:
             raise ValueError(f"frame {frame_idx} is outside the {geo.T}-frame geometry")
@@ -1201,7 +1243,22 @@ class MinimalV1LVGDiT:
                 ev = None
                 if self.attn_events is not None:
                     ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                if cp is None or cp_size == 1:
+                plan = self._sparse_plan(i, geo, cp_size if cp is not None else 1, kv, cv_nbrs)
+                if plan is not None:
+                    # sparse block: k normed + roped by the QKV GEMM as below, q by the separate (pre-scaling) pass, then
+                    # the box kernel on the column views of the token-major buffer, in place
+                    q_scale, attn_kw = self._self_attn_mode(i, hd)
+                    qkv = self._qkv_k_normed(h, i, n * Bs, Bs, cos, sin)
+                    N.head_rmsnorm_rope(qkv, n_rows=n * Bs, B=Bs, H=H, head_off=0,
+                                        weight=p[pre + "self_attn.q_norm.weight"], cos=cos, sin=sin, out_scale=q_scale)
+                    q3 = qkv.view(n, Bs, 3 * D)
+                    q, kk, vv = (q3[:, :, c * D:(c + 1) * D].view(n, Bs, H, hd).transpose(0, 1) for c in range(3))
+                    if ev is not None:
+                        ev[0].record()
+                    N.attn_na3d(q, kk, vv, plan, out=o.view(n, Bs, H, hd).transpose(0, 1),
+                                softmax_scale=attn_kw.get("softmax_scale"), prescaled=attn_kw.get("prescaled", False))
+                    lk = plan.keys_per_query
+                elif cp is None or cp_size == 1:
                     q_scale, attn_kw = self._self_attn_mode(i, hd)
                     # (a K/V cache: the measured key bound would cover this frame's keys only, so the weight bounds)
                     kslots = self._k_slots(attn_kw) if kv is None else None

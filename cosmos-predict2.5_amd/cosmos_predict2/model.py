@@ -365,8 +365,10 @@ class SamplingRun(_TokenState):
         # HIP graph of the DiT forward (model.hip_graph): captured at the second evaluation, after the first one ran
         # eagerly and built every lazily made buffer (RoPE tables, bf16 weight copies), then replayed on static copies
         # of the two inputs that change per evaluation (patch rows, timesteps); the context, the action and every
-        # weight stay the tensors the graph recorded. Not with CP (the K/V gathers run on their own streams).
-        self._graphable = bool(getattr(model, "hip_graph", False)) and net_fn is None and world == 1
+        # weight stay the tensors the graph recorded. Not with CP (the K/V gathers run on their own streams), nor for a
+        # net with sparse blocks (building a neighborhood plan copies host tables and synchronises).
+        self._graphable = (bool(getattr(model, "hip_graph", False)) and net_fn is None and world == 1
+                           and not getattr(model.net, "has_sparse_blocks", False))
         self._graph = None
         self.restart()
 

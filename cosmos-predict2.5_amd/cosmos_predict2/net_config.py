@@ -66,6 +66,25 @@ class DiTConfig:
     # the same frame, un-gated residual after an affine LayerNorm
     adaln_view_embedding: bool = False
     cross_view_attn_map: tuple = ()
+    # sparse self-attention (MiniTrainDIT(n_dense_blocks, natten_parameters), networks/minimal_v4_dit.py:1284-1289,
+    # 1349-1350, 1439-1441; replace_selfattn_op_with_sparse_attn_op :1743-1813): -1 = every block dense. Otherwise
+    # natten_parameters is one sparse_attn.NattenParams for every sparse block (0: all blocks sparse, 1: the middle block
+    # dense, n > 1: np.linspace(0, num_blocks - 1, n, dtype=int) dense) or a tuple of per-block NattenParams / None
+    # (None = dense). The reference's dicts and lists are converted to that hashable form on construction.
+    n_dense_blocks: int = -1
+    natten_parameters: tuple = ()
+
+    def __post_init__(self):
+        p = self.natten_parameters
+        if p is None or (isinstance(p, (list, tuple)) and len(p) == 0):
+            object.__setattr__(self, "natten_parameters", ())
+            return
+        from .sparse_attn import NattenParams  # (here: sparse_attn binds the native library, this module does not)
+
+        if isinstance(p, (list, tuple)):
+            object.__setattr__(self, "natten_parameters", tuple(NattenParams.of(x) for x in p))
+        else:
+            object.__setattr__(self, "natten_parameters", NattenParams.of(p))
 
     @property
     def head_dim(self) -> int:
@@ -199,6 +218,15 @@ SAMPLER_ACTION_STREAMING = SamplerConfig(sampler="dmd2_stream",
                                          trig_scaling="rectified_flow", sigma_data=1.0, sigma_conditional=0.0001,
                                          state_t=4, resolution="720", cache_frame_size=-1)
 
+# Sparse-attention nets: the sparsity the reference's "..._sparse-attn_7dense" (2B) and "..._9dense" (14B) experiments
+# put on the net (configs/video2world/experiment/resume_text2world/sparse_2B.py, sparse_14B.py): neighborhood window
+# (-1, 12, 24) = every frame, 12 x 24 patches, stride (1, 4, 8), given at the 720p patch grid (-1, 44, 80) and rescaled
+# to other grids; 7 of 28 / 9 of 36 blocks stay dense, spread evenly. 8.2 % of the keys per sparse block at 720p.
+# (Kept as plain values: DiTConfig converts them to sparse_attn.NattenParams.)
+NATTEN_720P_W12X24 = dict(window_size=(-1, 12, 24), stride=(1, 4, 8), base_size=(-1, 44, 80))
+DIT_2B_SPARSE_7DENSE = DIT_2B.replace(n_dense_blocks=7, natten_parameters=NATTEN_720P_W12X24)
+DIT_14B_SPARSE_9DENSE = DIT_14B.replace(n_dense_blocks=9, natten_parameters=NATTEN_720P_W12X24)
+
 # model name (cosmos_predict2/config.py ModelKey.name) -> (net, sampler)
 MODELS = {
     "2B/post-trained": (DIT_2B, SAMPLER_2B_POST_TRAINED),
@@ -213,6 +241,11 @@ MODELS = {
     "2B/distilled": (DIT_2B_DISTILLED, SAMPLER_2B_DISTILLED),
     # likewise no checkpoint key: the streaming action student trained with interactive/'s self-forcing recipe
     "2B/robot/action-cond/streaming": (DIT_2B_ACTION_STREAMING, SAMPLER_ACTION_STREAMING),
+    # the reference ships sparse attention as a net option plus training recipes on its EDM stage; it has no
+    # checkpoint key and no rectified-flow experiment for it, so (the footing of "2B/distilled") these entries serve a
+    # 2.5 net post-trained with that sparsity, under the rectified-flow samplers of 2B/post-trained / 14B/pre-trained
+    "2B/sparse-7dense": (DIT_2B_SPARSE_7DENSE, SAMPLER_2B_POST_TRAINED),
+    "14B/sparse-9dense": (DIT_14B_SPARSE_9DENSE, SAMPLER_PRE_TRAINED),
 }
 
 # Subset of VIDEO_RES_SIZE_INFO (cosmos_predict2/_src/predict2/datasets/utils.py:44-67); the model's

@@ -211,6 +211,25 @@ int cp25_attn_plan(int B, int H, int Lq, int Lk, int D);
  * form, or CP25_ERR_INVAL for another value. */
 int cp25_attn_cross_select(int form);
 
+/* 3D neighborhood attention: every query of the (T, Hg, Wg) token grid (token = (t Hg + h) Wg + w, L = T Hg Wg)
+ * attends the box of window[0] x window[1] x window[2] keys (dilation[i] apart along axis i) that the host plan
+ * assigns to its tile; softmax over those keys only, bf16 in / out, fp32 accumulation, P rounded to bf16 before P V.
+ * q / k / v / o: [B, L, H, D] addressed by {batch, token, head} element strides as cp25_attn_fwd takes them (the DiT's
+ * token-major [n, B, 3D] QKV buffer works in place); D must be 128, strides multiples of 8 elements, pointers 16-B
+ * aligned. The plan is two int32 device tables: q_tok [n_tiles][tile_rows] (tile_rows must be 128), the token id of
+ * each query row of a tile, -1 for an empty slot, slot 0 of every tile a real token; box [n_tiles][4], the first key
+ * index of the tile's box along t, h, w (fourth entry unused). All queries of a tile share the box, so the kernel
+ * applies no per-query mask; it clamps key tokens into [0, L) and skips q_tok entries outside it. window and dilation
+ * are host arrays of 3 ints with window[i] * dilation[i] <= extent[i] (else CP25_ERR_INVAL, as for D != 128 or bad
+ * strides). prescaled != 0: q rows already carry softmax_scale * log2(e) (cp25_head_rmsnorm_rope_scaled) and
+ * softmax_scale is unused. Replaces: NeighborhoodAttention.forward (modules/neighborhood_attn.py:172-252, NATTEN's
+ * neighborhood_attention_generic; CUDA compute capabilities 80 / 90 / 100 only) as plugged in by NattenA2AAttnOp
+ * (networks/a2a_cp.py:222-226) through replace_selfattn_op_with_sparse_attn_op (minimal_v4_dit.py:1743-1813). */
+int cp25_attn_na3d(const void* q, const void* k, const void* v, void* o, int B, int H, int T, int Hg, int Wg, int D,
+                   const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                   const int64_t* o_strides, const int* q_tok, const int* box, int n_tiles, int tile_rows,
+                   const int* window, const int* dilation, float softmax_scale, int prescaled, hipStream_t stream);
+
 /* ---------------------------------------------------------------- DiT block elementwise
  * Activations are token-major [n_tok, B, D] bf16 (batch inner). Row (tok, b) uses modulation row
  * (b, t) with t = (tok0 + tok) / hw (frame index; tok0 = first global token of this CP shard).
