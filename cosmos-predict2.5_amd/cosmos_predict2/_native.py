@@ -92,6 +92,11 @@ SIGNATURES = {
                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _F, _I, _P],
     "cp25_ln_mod": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _P, _I64, _I, _I, _I64, _I64, _F, _P],
     "cp25_ln_mod_fp8": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _I64, _I, _I, _I64, _I64, _F, _P],
+    "cp25_ln_mod_cam": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _I, _I, _I64, _I64, _F,
+                        _P],
+    "cp25_ln_mod_cam_fp8": [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _I64, _I, _I, _I64,
+                            _I64, _F, _P],
+    "cp25_plucker_tokens": [_P, _P, _P, _I, _I, _I, _P],
     "cp25_final_ln_mod": [_P, _P, _P, _I64, _I64, _P, _P, _I64, _I64, _P, _I64, _I, _I, _I64, _I64, _F, _P],
     "cp25_layer_norm": [_P, _I64, _P, _P, _P, _I64, _I64, _I, _F, _P],
     "cp25_head_rmsnorm_rope": [_P, _I64, _I64, _I, _I, _I, _P, _P, _P, _P, _I64, _F, _P],
@@ -521,38 +526,83 @@ def _check_mask(frame_mask: torch.Tensor, *, n_tok: int, tok0: int, hw: int) -> 
         raise ValueError(f"tokens [{tok0}, {tok0 + n_tok}) with hw={hw} exceed the {frame_mask.numel()}-frame mask")
 
 
+def _check_cam(cam: torch.Tensor, cam_st: int, cam_sb: int, *, n_tok: int, B: int, D: int, device) -> None:
+    """The camera kernels read D elements at cam[tok * cam_st + b * cam_sb] for tok < n_tok, b < B: all of them must
+    lie inside the view `cam` describes (as _check_frames does for the modulation)."""
+    if cam.dtype != torch.bfloat16 or cam.device != device:
+        raise ValueError("cam must be a bf16 tensor on the activations' device")
+    if cam_st < D or cam_sb < 0 or cam_st % 8 or cam_sb % 8:
+        raise ValueError(f"cam strides ({cam_st}, {cam_sb}): cam_st >= D = {D}, both multiples of 8 elements")
+    extent = 1 + sum((n - 1) * st for n, st in zip(cam.shape, cam.stride())) if cam.numel() else 0
+    reach = (n_tok - 1) * cam_st + (B - 1) * cam_sb + D
+    if n_tok and reach > extent:
+        raise ValueError(f"cam {tuple(cam.shape)} (strides {cam.stride()}) does not cover rows [0, {n_tok}) x B={B} "
+                         f"at strides ({cam_st}, {cam_sb})")
+
+
 def ln_mod(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, *, n_tok: int, B: int, tok0: int, hw: int,
            x_st: int, x_sb: int, y: Optional[torch.Tensor] = None, gate: Optional[torch.Tensor] = None,
            x_out: Optional[torch.Tensor] = None, h_out: Optional[torch.Tensor] = None,
-           eps: float = 1e-6, fp8: bool = False):
+           eps: float = 1e-6, fp8: bool = False, cam: Optional[torch.Tensor] = None, cam_st: Optional[int] = None,
+           cam_sb: int = 0):
     """h = LN(x [+ gate*y]) * (1 + scale) + shift over token-major [n_tok, B, D] bf16 rows.
     shift/scale/gate are bf16 views [B, T, D] (strides (sb, st, 1), shared by all three).
     fp8=True returns h as the row-scaled fp8 GEMM operand (q [n_tok*B, D] float8_e4m3fn, scale
-    [n_tok*B, 1] fp32) instead (cp25_ln_mod_fp8)."""
+    [n_tok*B, 1] fp32) instead (cp25_ln_mod_fp8).
+    cam (the camera net's per-token embedding, cp25_ln_mod_cam / _fp8): h = bf16(h + cam[tok * cam_st + b * cam_sb]),
+    tok the local token; cam_st defaults to cam.stride(0), cam_sb = 0 shares the rows across the batch."""
     lib = load_library()
     D = shift.shape[-1]
     _check_frames(shift, n_tok=n_tok, B=B, tok0=tok0, hw=hw)
     if shift.stride() != scale.stride() or (gate is not None and gate.stride() != shift.stride()):
         raise ValueError("shift/scale/gate must share strides")
+    cam_args = ()
+    sfx = ""
+    if cam is not None:
+        cam_st = cam.stride(0) if cam_st is None else cam_st
+        _check_cam(cam, cam_st, cam_sb, n_tok=n_tok, B=B, D=D, device=x.device)
+        cam_args = (_ptr(cam), cam_st, cam_sb)
+        sfx = "_cam"
     if fp8:
         q = torch.empty((n_tok * B, D), dtype=torch.float8_e4m3fn, device=x.device)
         s = torch.empty((n_tok * B, 1), dtype=torch.float32, device=x.device)
-        rc = lib.cp25_ln_mod_fp8(
+        rc = getattr(lib, f"cp25_ln_mod{sfx}_fp8")(
             _ptr(x), x_st, x_sb, _ptr(y), _ptr(gate), _ptr(shift), _ptr(scale), shift.stride(0), shift.stride(1),
-            _ptr(x_out), _ptr(q), _ptr(s), n_tok, B, D, tok0, hw, eps, _stream(x.device),
+            *cam_args, _ptr(x_out), _ptr(q), _ptr(s), n_tok, B, D, tok0, hw, eps, _stream(x.device),
         )
-        _check("cp25_ln_mod_fp8", rc)
+        _check(f"cp25_ln_mod{sfx}_fp8", rc)
         return q, s
     if h_out is None:
         h_out = torch.empty((n_tok, B, D), dtype=torch.bfloat16, device=x.device)
-    if shift.stride() != scale.stride() or (gate is not None and gate.stride() != shift.stride()):
-        raise ValueError("shift/scale/gate must share strides")
-    rc = lib.cp25_ln_mod(
+    rc = getattr(lib, f"cp25_ln_mod{sfx}")(
         _ptr(x), x_st, x_sb, _ptr(y), _ptr(gate), _ptr(shift), _ptr(scale), shift.stride(0), shift.stride(1),
-        _ptr(x_out), _ptr(h_out), n_tok, B, D, tok0, hw, eps, _stream(x.device),
+        *cam_args, _ptr(x_out), _ptr(h_out), n_tok, B, D, tok0, hw, eps, _stream(x.device),
     )
-    _check("cp25_ln_mod", rc)
+    _check(f"cp25_ln_mod{sfx}", rc)
     return h_out
+
+
+def plucker_tokens(w2c: torch.Tensor, intrinsics: torch.Tensor, Hp: int, Wp: int,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cp25_plucker_tokens: w2c [F, 3, 4] and intrinsics [F, 4] (fx, fy, cx, cy at (16 Hp, 16 Wp) pixels), fp32 device
+    tensors -> [F * Hp * Wp, 1536] bf16 rows (tokens (frame, hp, wp), features "(c m n)", c over [moment | direction])."""
+    lib = load_library()
+    if w2c.dim() != 3 or tuple(w2c.shape[1:]) != (3, 4) or tuple(intrinsics.shape) != (w2c.shape[0], 4):
+        raise ValueError(f"plucker_tokens: w2c [F, 3, 4] and intrinsics [F, 4], got {tuple(w2c.shape)}, "
+                         f"{tuple(intrinsics.shape)}")
+    if w2c.dtype != torch.float32 or intrinsics.dtype != torch.float32 or intrinsics.device != w2c.device:
+        raise ValueError("plucker_tokens: fp32 poses and intrinsics on one device")
+    if Hp <= 0 or Wp <= 0 or w2c.shape[0] == 0:
+        raise ValueError(f"plucker_tokens: empty grid ({w2c.shape[0]}, {Hp}, {Wp})")
+    F = w2c.shape[0]
+    w2c, intrinsics = w2c.contiguous(), intrinsics.contiguous()
+    if out is None:
+        out = torch.empty((F * Hp * Wp, 1536), dtype=torch.bfloat16, device=w2c.device)
+    if out.dtype != torch.bfloat16 or tuple(out.shape) != (F * Hp * Wp, 1536) or not out.is_contiguous():
+        raise ValueError("plucker_tokens: out must be a contiguous bf16 [F * Hp * Wp, 1536]")
+    _check("cp25_plucker_tokens", lib.cp25_plucker_tokens(_ptr(w2c), _ptr(intrinsics), _ptr(out), F, Hp, Wp,
+                                                          _stream(w2c.device)))
+    return out
 
 
 def final_ln_mod(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, *, n_tok: int, B: int, tok0: int, hw: int,

@@ -25,7 +25,7 @@ from .pipeline import DEFAULT_NEGATIVE_PROMPT
 IMAGE_EXTENSIONS = [".png", ".jpg", ".jpeg", ".webp"]
 VIDEO_EXTENSIONS = [".mp4"]
 ModelName = Literal["2B/post-trained", "2B/pre-trained", "14B/pre-trained", "2B/distilled",
-                    "2B/robot/action-cond/streaming", "2B/sparse-7dense", "14B/sparse-9dense"]
+                    "2B/robot/action-cond/streaming", "2B/sparse-7dense", "14B/sparse-9dense", "2B/camera-cond"]
 
 
 def is_rank0() -> bool:

@@ -73,6 +73,8 @@ def state_dict_shapes(cfg: DiTConfig) -> Dict[str, Tuple[Tuple[int, ...], torch.
             s[p + "cross_view_attn.k_norm.weight"] = ((hd,), BF16)
             s[p + "layer_norm_cross_view_attn.weight"] = ((D,), BF16)
             s[p + "layer_norm_cross_view_attn.bias"] = ((D,), BF16)
+        if cfg.camera_dim:  # camera Block (camera/networks/minimal_v4_dit_camera_conditioned.py:1079-1080)
+            s[p + "cam_encoder.weight"] = ((D, cfg.camera_dim), BF16)
         s[p + "mlp.layer1.weight"] = ((cfg.mlp_hidden, D), BF16)
         s[p + "mlp.layer2.weight"] = ((D, cfg.mlp_hidden), BF16)
         for m in ("self_attn", "cross_attn", "mlp"):
@@ -136,6 +138,9 @@ def init_state_dict(cfg: DiTConfig, seed: int = 0, device="cpu", zero_adaln_out:
         elif name.startswith("crossattn_proj"):
             bound = 1.0 / math.sqrt(cfg.crossattn_proj_in_channels)
             out[name] = (torch.rand(shape, generator=g, device=device) * 2 - 1).mul_(bound).to(BF16)
+        elif name.endswith("cam_encoder.weight"):
+            # std 1 / sqrt(x_dim), not of the fan-in (camera/networks/minimal_v4_dit_camera_conditioned.py:1117-1119)
+            out[name] = tn(shape, 1.0 / math.sqrt(D))
         elif name.endswith(".2.weight") and "adaln_modulation" in name and zero_adaln_out:
             out[name] = torch.zeros(shape, dtype=BF16, device=device)
         else:
@@ -174,6 +179,19 @@ class ContextCache:
     B: int
     k: List[torch.Tensor]  # [B, Lctx, H, hd] bf16 (normed)
     v: List[torch.Tensor]  # [B, Lctx, H, hd] bf16
+
+
+@dataclass
+class CameraCache:
+    """Per-trajectory constants of a camera-conditioned net (prepare_camera): the camera feature rows and, with
+    mode "all", every block's cam_encoder output. The CFG pair shares it (the camera conditioner key has no dropout,
+    camera/configs/camera_conditioned/conditioner.py:42-68), so there is no batch dimension."""
+
+    n_tok: int
+    rows: torch.Tensor                    # [n_tok, camera_dim] bf16, token-major
+    mode: str                             # "all": emb holds the blocks' embeddings; "none": recomputed into buf
+    emb: Optional[List[torch.Tensor]]     # per block [n_tok, D] bf16
+    buf: Optional[torch.Tensor] = None    # "none": the one [n_tok, D] buffer every block's embedding is made in
 
 
 @dataclass
@@ -330,6 +348,21 @@ class MinimalV1LVGDiT:
             raise NotImplementedError("sparse (neighborhood) self-attention is not built for multi-view / cross-view "
                                       "nets")
         self._na_plans = PlanCache(self.device)
+        # camera-conditioned net (cfg.camera_dim): "all" (default) holds every block's cam_encoder output for the whole
+        # trajectory (num_blocks x n_tok x D bf16: ~29 GB at the 2B experiment's 253 440 tokens), "none" recomputes
+        # block i's into one reusable buffer at each evaluation (prepare_camera); the outputs are bit-identical
+        self.camera_cache = "all"
+        if cfg.camera_dim:
+            for other, what in ((self.has_sparse_blocks, "sparse (neighborhood) blocks"),
+                                (cfg.action_dim, "action embedders"),
+                                (cfg.n_cameras_emb or cfg.cross_view_attn_map or cfg.adaln_view_embedding,
+                                 "a multi-view net")):
+                if other:
+                    raise ValueError(f"a camera-conditioned net (camera_dim = {cfg.camera_dim}) combined with {what} "
+                                     "is not built")
+            if not N.gemm_supported(cfg.model_channels, cfg.camera_dim):
+                raise ValueError(f"cam_encoder weight [{cfg.model_channels}, {cfg.camera_dim}]: the own GEMM needs "
+                                 "N % 256 == 0 and K % 64 == 0")
 
     def set_linear_precision(self, precision: str) -> None:
         """"bf16" (default, the reference's arithmetic) or "fp8": the 28 blocks' q/k/v, output, cross-q,
@@ -468,12 +501,15 @@ class MinimalV1LVGDiT:
         return qkv
 
     def _proj_res(self, a, w: torch.Tensor, key: str, x: torch.Tensor, x_st: int, x_sb: int, gate: torch.Tensor,
-                  B: int, geo: "Geometry", n: int, lnk: dict, shift=None, scale=None, gelu_in: bool = False):
+                  B: int, geo: "Geometry", n: int, lnk: dict, shift=None, scale=None, gelu_in: bool = False,
+                  cam: Optional[torch.Tensor] = None):
         """x' = x + gate * (a w^T) (Block.forward's gated residuals, minimal_v4_dit.py:1204, 1237, 1246) for the token-
         major [n, B, D] rows, then (if shift is given) h = LN-mod(x') for the next sub-layer. Own GEMM: the residual
         rides in its epilogue (cp25_gemm_res) and the LN-mod reads x' only; else the plain own GEMM + the residual
-        in cp25_ln_mod. Returns (x' [n, B, D], h or None)."""
+        in cp25_ln_mod. cam [n, D]: the next block's camera embedding, added to h (cp25_ln_mod_cam) on either path.
+        Returns (x' [n, B, D], h or None)."""
         D = w.shape[0]
+        lnk = lnk if cam is None else dict(lnk, cam=cam)
         fused = None
         path = self._fused_res(a, w, B, geo.hw)
         if path == 1:
@@ -673,6 +709,46 @@ class MinimalV1LVGDiT:
             ks.append(k.view(B, Lc, H, hd))
             vs.append(v.view(B, Lc, H, hd))
         return ContextCache(B=B, k=ks, v=vs)
+
+    @torch.no_grad()
+    def prepare_camera(self, camera_rows: torch.Tensor, geo: Geometry,
+                       camera_cache: Optional[str] = None) -> CameraCache:
+        """camera_rows [n_tok, camera_dim] (or the reference's [T, Hp, Wp, camera_dim] patch-grid tensor, one batch
+        entry: camera/networks/minimal_v4_dit_camera_conditioned.py:1650-1658 hands the same tensor to every block)
+        -> the per-trajectory camera constants. camera_cache (default: self.camera_cache) "all" computes every block's
+        cam_emb_i = camera_rows W_i^T (:1189, a bf16 Linear: cp25_gemm_epi, bf16 under linear_precision "fp8" too) once
+        and holds them; "none" keeps only the rows and one [n_tok, D] buffer that each block's embedding is recomputed
+        into at every evaluation. Same GEMM either way, so the two give bit-identical forwards."""
+        cfg = self.cfg
+        if not cfg.camera_dim:
+            raise ValueError("prepare_camera on a net without cam_encoder (camera_dim = 0)")
+        mode = self.camera_cache if camera_cache is None else camera_cache
+        if mode not in ("all", "none"):
+            raise ValueError(f"camera_cache must be 'all' or 'none', got {mode!r}")
+        if camera_rows.dim() == 4:
+            camera_rows = camera_rows.reshape(-1, camera_rows.shape[-1])
+        n = geo.n_tok or geo.L
+        if camera_rows.dim() != 2 or tuple(camera_rows.shape) != (n, cfg.camera_dim):
+            raise ValueError(f"camera rows {tuple(camera_rows.shape)}: expected [{n}, {cfg.camera_dim}] for the "
+                             f"{geo.T} x {geo.Hp} x {geo.Wp} patch grid")
+        if geo.tok0 != 0 or n != geo.L or geo.frames is not None:
+            raise ValueError("a camera-conditioned net combined with context parallelism (a token shard) is not built")
+        rows = camera_rows.to(device=self.device, dtype=BF16).contiguous()
+        D = cfg.model_channels
+        if mode == "none":
+            return CameraCache(n_tok=n, rows=rows, mode=mode, emb=None,
+                               buf=torch.empty((n, D), dtype=BF16, device=self.device))
+        emb = [N.gemm_epi(rows, self.sd[f"blocks.{i}.cam_encoder.weight"]) for i in range(cfg.num_blocks)]
+        return CameraCache(n_tok=n, rows=rows, mode=mode, emb=emb)
+
+    def _cam_emb(self, camera: Optional[CameraCache], i: int) -> Optional[torch.Tensor]:
+        """Block i's camera embedding [n_tok, D] (None without camera): the cached one, or recomputed into the
+        cache's one buffer (stream order keeps the previous block's reader ahead of this write)."""
+        if camera is None:
+            return None
+        if camera.emb is not None:
+            return camera.emb[i]
+        return N.gemm_epi(camera.rows, self.sd[f"blocks.{i}.cam_encoder.weight"], out=camera.buf)
 
     def _bias_linear(self, x: torch.Tensor, key: str, epilogue: int = 0) -> Optional[torch.Tensor]:
         """bf16 nn.Linear with bias (weight / bias `key`.weight / .bias) of x [M, K] on the hand-written GEMM: the bias
@@ -951,12 +1027,15 @@ class MinimalV1LVGDiT:
     def forward_tokens(self, patch_rows: torch.Tensor, t_B_T: torch.Tensor, ctx: ContextCache,
                        geo: Geometry, action: Optional[torch.Tensor] = None,
                        view_indices: Optional[torch.Tensor] = None, shared_batch: bool = False,
-                       rows_k128: bool = False) -> torch.Tensor:
+                       rows_k128: bool = False, camera: Optional[CameraCache] = None) -> torch.Tensor:
         """patch_rows: [n_tok, Bx, 72] bf16 (Bx = 1 shares the input across the CFG batch; rows_k128: made by
         patchify(ld=128), see embed_patches);
         t_B_T: [B, T] fp32, already scaled. Returns the final layer output [n_tok, B, 64] fp32
         (feature order (p1 p2 C) = patch layout). shared_batch: the caller guarantees every batch entry
         has the same t (and action), so with Bx = 1 they differ only in the text context (_blocks).
+        camera (prepare_camera; camera-conditioned nets): every block's self-attention reads
+        bf16(h + cam_emb_i[token]) (camera/networks/minimal_v4_dit_camera_conditioned.py:1189-1194), the same camera in
+        every batch entry, so the shared block-0 prefix stays valid. Single GPU only.
 
         CP = 1: one pass over the batch (B = 2 = [cond, uncond]).
         CP > 1: the batch entries run as two software-pipelined lanes on the current stream: each
@@ -971,6 +1050,16 @@ class MinimalV1LVGDiT:
         D = cfg.model_channels
         n = geo.n_tok
         Bx = patch_rows.shape[1]
+        if cfg.camera_dim:
+            if camera is None:
+                raise ValueError("this camera-conditioned net needs `camera` (prepare_camera)")
+            if self.cp_group is not None or self.force_lanes:
+                raise ValueError("a camera-conditioned net combined with context parallelism is not built")
+            if camera.n_tok != n or geo.tok0 != 0 or geo.frames is not None:
+                raise ValueError(f"the camera cache holds {camera.n_tok} tokens, the geometry {n} from token "
+                                 f"{geo.tok0}")
+        elif camera is not None:
+            raise ValueError("`camera` given to a net without cam_encoder (camera_dim = 0)")
         x_in = self.embed_patches(patch_rows, geo, view_indices, rows_k128=rows_k128)
         mods, shift_f, scale_f = self.time_modulation(t_B_T, action)
         cos, sin = self.rope_tables(geo)
@@ -993,7 +1082,7 @@ class MinimalV1LVGDiT:
             cv = self._cross_view_neighbours(geo, view_indices)
         if B == 1 or (cp_size == 1 and not self.force_lanes) or (cv is not None and cp_size == 1):
             gen = self._blocks(x_in, mods, shift_f, scale_f, ctx, geo, cos, sin, cp, cp_size, shared_batch,
-                               cv_nbrs=cv)
+                               cv_nbrs=cv, camera=camera)
             while True:
                 try:
                     next(gen)
@@ -1064,6 +1153,8 @@ class MinimalV1LVGDiT:
         the slot is none of the history's. store=True also marks the frame as stored: frames are stored in order, and
         frame t runs only once frames 0 .. t - 1 are."""
         cfg = self.cfg
+        if cfg.camera_dim:
+            raise ValueError("a camera-conditioned net combined with forward_frame (the K/V cache) is not built")
         if cfg.use_wan_fp32_strategy or cfg.n_cameras_emb or cfg.cross_view_attn_map:
             raise ValueError("forward_frame serves the causal student's net: bf16 conditioning "
                              "(use_wan_fp32_strategy=False), one view")
@@ -1189,7 +1280,8 @@ class MinimalV1LVGDiT:
                               pre + "cross_view_attn.output_proj", x, B * D, D, gate1, B, geo, n, lnk, shift, scale)
 
     def _blocks(self, x_in, mods, shift_f, scale_f, ctx: ContextCache, geo: Geometry, cos, sin, cp, cp_size,
-                shared_batch: bool = False, prefix=None, prefix_only: bool = False, cv_nbrs=None, kv=None):
+                shared_batch: bool = False, prefix=None, prefix_only: bool = False, cv_nbrs=None, kv=None,
+                camera: Optional[CameraCache] = None):
         """Generator: issues the 28 blocks + final layer for the batch entries in x_in/mods/ctx on the
         current stream; returns the final layer output [n, B, 64] fp32. Yields (so the caller can
         issue the other lane) right after each self-attention K/V gather is queued (CP > 1), or after
@@ -1223,11 +1315,15 @@ class MinimalV1LVGDiT:
         common = dict(n_tok=n, B=B, tok0=geo.tok0, hw=geo.hw)
         lnk = dict(common, fp8=self.linear_precision == "fp8")
         lnk1 = dict(lnk, B=1)
+
+        def cam_kw(i):  # the cam operand of the LN-mod that makes block i's self-attention input (camera nets only)
+            return {} if camera is None else dict(cam=self._cam_emb(camera, i))
+
         if prefix is None:
             sh, sc, _ = mod(0, 0, 1 if share0 else None)
             x = x_in
             h = N.ln_mod(x, sh, sc, x_st=x_in.stride(0), x_sb=0 if Bx == 1 else x_in.stride(1),
-                         **(lnk1 if share0 else lnk))
+                         **cam_kw(0), **(lnk1 if share0 else lnk))
         else:
             x, h = prefix
         y = None
@@ -1340,6 +1436,7 @@ class MinimalV1LVGDiT:
             _, _, g_ml = mod(i, 2)
             last = i + 1 == cfg.num_blocks
             sh, sc = (None, None) if last else mod(i + 1, 0)[:2]
+            cam_next = {} if last else cam_kw(i + 1)  # added to the next block's self-attention input
             if self._own(h1, w1):
                 # layer1 + exact-erf GELU in one hand-written MFMA GEMM (the epilogue applies it to the bf16 product, as
                 # cp25_gelu would): the [n B, 4 D] hidden makes one HBM trip instead of three
@@ -1348,14 +1445,14 @@ class MinimalV1LVGDiT:
                 u = self._linear(h1, w1, pre + "mlp.layer1")
             if self._fused_res(u, w2, B, geo.hw):
                 x, h = self._proj_res(u, w2, pre + "mlp.layer2", x, B * D, D, g_ml, B, geo, n, lnk, sh, sc,
-                                      gelu_in=self.linear_precision == "fp8")
+                                      gelu_in=self.linear_precision == "fp8", **cam_next)
                 y, gate_prev = None, None
             else:
                 y = self._linear(u, w2, pre + "mlp.layer2", gelu_in=self.linear_precision != "bf16")
                 gate_prev = g_ml
                 if not last:
                     x_new = torch.empty((n, B, D), dtype=BF16, device=self.device)
-                    h = N.ln_mod(x, sh, sc, x_st=B * D, x_sb=D, y=y, gate=gate_prev, x_out=x_new, **lnk)
+                    h = N.ln_mod(x, sh, sc, x_st=B * D, x_sb=D, y=y, gate=gate_prev, x_out=x_new, **cam_next, **lnk)
                     x = x_new
             del u
             if cp is None or cp_size == 1:
@@ -1497,8 +1594,16 @@ class MinimalV1LVGDiT:
         t = self.scale_timesteps(timesteps_B_T)
         if t.shape[1] == 1 and T > 1:
             t = t.expand(B, T).contiguous()
+        cam = kwargs.get("camera")
+        if cam is not None:
+            # camera [B, T, Hp, Wp, camera_dim] (CameraConditionedMinimalV1LVGDiT.forward): one camera for the batch
+            if cam.dim() == 5:
+                if cam.shape[0] != 1 and not all(torch.equal(cam[0], cam[b]) for b in range(1, cam.shape[0])):
+                    raise ValueError("per-entry cameras in one batch are not built: the batch shares one camera")
+                cam = cam[0]
+            cam = self.prepare_camera(cam, geo)
         out = self.forward_tokens(rows.contiguous(), t, ctx, geo, action=action,
-                                  view_indices=view_indices)  # [L, B, 64] (p1 p2 C)
+                                  view_indices=view_indices, camera=cam)  # [L, B, 64] (p1 p2 C)
         out = out.view(T, Hp, Wp, B, 2, 2, C).permute(3, 6, 0, 1, 4, 2, 5)
         return out.reshape(B, C, T, Hl, Wl).float()
 

@@ -183,6 +183,47 @@ class Video2WorldModelRectifiedFlow:
         return run.latents()
 
     @torch.no_grad()
+    def generate_camera_samples(self, ctx_cond: torch.Tensor, ctx_uncond: torch.Tensor, camera: torch.Tensor, *,
+                                source_video: Optional[torch.Tensor] = None,
+                                source_latent: Optional[torch.Tensor] = None, num_conditional_frames: int = 1,
+                                guidance: float = 1.5, seed: int = 1, num_steps: int = 35, shift: float = 5.0,
+                                camera_cache: Optional[str] = None, net_fn=None, progress=None):
+        """Camera-conditioned Video2World (CameraSamplingRun): the source clip as source_video [1, 3, T_pix, H, W]
+        (uint8 or [-1, 1]; encoded whole by the tokenizer, camera_conditioned_video2world_model_rectified_flow.py:
+        199-203) or as source_latent [1, C, T_seg, H, W]; camera the per-token features of the three clips in the
+        order they arrive in the reference's data batch, [source | target 0 | target 1] along the frame axis
+        ([3 T_seg, Hp, Wp, camera_dim], or with a leading batch dimension of 1), reordered here to the latent axis's
+        [target 0 | source | target 1] (:186-188). Returns the (target 0, target 1) latents, [1, C, T_seg, H, W] fp32."""
+        from .camera import reorder_source_first
+
+        if (source_video is None) == (source_latent is None):
+            raise ValueError("give exactly one of source_video / source_latent")
+        if source_latent is None:
+            if self.pixel_path == "device" and source_video.dtype == torch.uint8:
+                source_latent = self.tokenizer.encode_u8(source_video.to(self.device))
+            else:
+                source_latent = self.encode(self._normalize_video(source_video))
+        source_latent = source_latent.contiguous().float()
+        _, C, Ts, H, W = source_latent.shape
+        cam = camera[0] if camera.dim() == 5 and camera.shape[0] == 1 else camera
+        if cam.dim() != 4 or tuple(cam.shape[:3]) != (3 * Ts, H // 2, W // 2):
+            raise ValueError(f"camera {tuple(camera.shape)}: expected [{3 * Ts}, {H // 2}, {W // 2}, camera_dim] for "
+                             f"three {Ts}-frame segments")
+        cam = reorder_source_first(cam, dim=0)
+        cache = None
+        if net_fn is None:
+            geo = Geometry(T=3 * Ts, Hp=H // 2, Wp=W // 2, tok0=0, n_tok=3 * Ts * (H // 2) * (W // 2))
+            cache = self.net.prepare_camera(cam.to(self.device), geo, camera_cache)
+        run = CameraSamplingRun(self, source_latent, ctx_cond, ctx_uncond, cache,
+                                num_conditional_frames=num_conditional_frames, guidance=guidance, seed=seed,
+                                num_steps=num_steps, shift=shift, net_fn=net_fn)
+        while not run.done:
+            i = run.step()
+            if progress is not None:
+                progress(i, run.num_evals)
+        return run.target_latents()
+
+    @torch.no_grad()
     def generate_samples_from_batch(self, data_batch: Dict, guidance: float = 1.5, seed: int = 1,
                                     state_shape=None, n_sample: Optional[int] = None,
                                     is_negative_prompt: bool = False, num_steps: int = 35, shift: float = 5.0,
@@ -275,7 +316,10 @@ class _TokenState:
     conditioning-frame mask and the ground-truth latent in patch layout, and the gather back to [1, C, T, H, W]."""
 
     def _setup_state(self, model: "Video2WorldModelRectifiedFlow", gt, state_shape, num_conditional_frames: int,
-                     seed: int, init_noise: Optional[torch.Tensor] = None) -> None:
+                     seed: int, init_noise: Optional[torch.Tensor] = None,
+                     frame_mask: Optional[torch.Tensor] = None) -> None:
+        """frame_mask [T]: an explicit conditioning-frame mask (the camera sampler's), instead of the first
+        num_conditional_frames frames of every view."""
         self.model = model
         C, T, H, W = state_shape
         self.state_shape = (C, T, H, W)
@@ -304,8 +348,14 @@ class _TokenState:
             noise_full = init_noise.to(dev, torch.float32)
         self.noise = to_patch_layout(noise_full[0])[sl].contiguous()
         del noise_full
-        frame_mask = torch.zeros(T, dtype=torch.float32, device=dev)
-        if geo.T_view > 1 and num_conditional_frames > 0:
+        explicit = frame_mask is not None
+        if explicit:
+            if frame_mask.numel() != T:
+                raise ValueError(f"frame_mask has {frame_mask.numel()} entries for {T} latent frames")
+            frame_mask = frame_mask.reshape(T).to(dev, torch.float32).contiguous()
+        else:
+            frame_mask = torch.zeros(T, dtype=torch.float32, device=dev)
+        if not explicit and geo.T_view > 1 and num_conditional_frames > 0:
             # the first frames of every view (multi-view FIRST_RANDOM_N, predict2_multiview/configs/vid2vid/
             # defaults/conditioner.py:125-260; one view: video2world conditioner.py:45-143)
             for vi in range(geo.n_views):
@@ -345,9 +395,16 @@ class SamplingRun(_TokenState):
 
     def __init__(self, model: "Video2WorldModelRectifiedFlow", gt, ctx_cond, ctx_uncond, *, state_shape,
                  num_conditional_frames: int, guidance: float, seed: int, num_steps: int, shift: float = 5.0,
-                 cfg_mode: Optional[str] = None, net_fn=None, action=None, view_indices=None):
-        self._setup_state(model, gt, state_shape, num_conditional_frames, seed)
+                 cfg_mode: Optional[str] = None, net_fn=None, action=None, view_indices=None,
+                 init_noise: Optional[torch.Tensor] = None, frame_mask: Optional[torch.Tensor] = None, camera=None):
+        """init_noise, frame_mask: the initial state and the conditioning-frame mask given explicitly (_setup_state);
+        camera: the camera-conditioned net's dit.CameraCache, handed to every forward (CameraSamplingRun sets all
+        three)."""
+        self._setup_state(model, gt, state_shape, num_conditional_frames, seed, init_noise, frame_mask)
         dev, geo, world = model.device, self.geo, self.world
+        if camera is not None and world > 1:
+            raise ValueError("a camera-conditioned net combined with context parallelism is not built")
+        self.camera = camera
 
         self.net_fn = net_fn
         self.ctx = None if net_fn is not None else model.net.prepare_context(torch.cat([ctx_cond, ctx_uncond], 0))
@@ -366,9 +423,10 @@ class SamplingRun(_TokenState):
         # eagerly and built every lazily made buffer (RoPE tables, bf16 weight copies), then replayed on static copies
         # of the two inputs that change per evaluation (patch rows, timesteps); the context, the action and every
         # weight stay the tensors the graph recorded. Not with CP (the K/V gathers run on their own streams), nor for a
-        # net with sparse blocks (building a neighborhood plan copies host tables and synchronises).
+        # net with sparse blocks (building a neighborhood plan copies host tables and synchronises), nor for camera runs
+        # (out of scope).
         self._graphable = (bool(getattr(model, "hip_graph", False)) and net_fn is None and world == 1
-                           and not getattr(model.net, "has_sparse_blocks", False))
+                           and not getattr(model.net, "has_sparse_blocks", False) and camera is None)
         self._graph = None
         self.restart()
 
@@ -404,7 +462,8 @@ class SamplingRun(_TokenState):
 
             def forward(rows_, t_):
                 return m.net.forward_tokens(rows_, t_, self.ctx, geo, action=self.action,
-                                            view_indices=self.view_indices, shared_batch=shared, rows_k128=True)
+                                            view_indices=self.view_indices, shared_batch=shared, rows_k128=True,
+                                            camera=self.camera)
             if self._graphable and self.i >= 1:
                 # rows is the [n, 72] view of patchify's zero-padded [n, 128] buffer (rows_k128): the static copy
                 # keeps that layout, pad columns included
@@ -429,6 +488,62 @@ class SamplingRun(_TokenState):
         self.sched.step_(v, t)
         self.i += 1
         return self.i - 1
+
+
+def camera_frame_mask(T: int, num_conditional_frames: int) -> torch.Tensor:
+    """set_camera_conditioned_video_condition (camera/configs/camera_conditioned/conditioner.py:42-68): ones on
+    latent frames [n, 2n) of the whole three-segment time axis, the literal rule for any n (an image batch, T == 1,
+    conditions nothing) -> [T] fp32."""
+    m = torch.zeros(T, dtype=torch.float32)
+    if T > 1:
+        n = int(num_conditional_frames)
+        m[n: 2 * n] += 1
+    return m
+
+
+class CameraSamplingRun(SamplingRun):
+    """One trajectory of the camera-conditioned Video2World model: one source clip and two target camera trajectories
+    in, two re-rendered clips out (CameraConditionedVideo2WorldModelRectifiedFlow.generate_samples_from_batch and
+    get_velocity_fn_from_batch, camera/models/camera_conditioned_video2world_model_rectified_flow.py:155-327).
+
+    The latent time axis is three equal segments [target 0 | source | target 1] (:296):
+        gt = cat(0, source latent, 0) (:205); the mask is 1 on frames [n, 2n), n = num_conditional_frames
+        (camera_frame_mask); the initial state and denoise's `noise` are both cat(noise, source latent, noise), the two
+        target segments drawing the same seeded noise (:286-296); CFG cond + g (cond - uncond) (:230); timesteps
+        set_timesteps(num_steps, shift=shift), no Karras sigmas (:301); the UniPC step runs on all frames (:316-319).
+    Everything per evaluation is SamplingRun.step(): the patchify / cfg_velocity / UniPC kernels index the per-frame
+    mask as given. camera: the net's CameraCache over the 3 T_seg frames in the segment order above (the same in both
+    CFG branches: the conditioner's camera key has dropout 0), or None with a stub net_fn.
+    source_latent [1, C, T_seg, H, W]. target_latents() = chunk(latents, 3, dim=2)[0] and [2] (:324-325)."""
+
+    def __init__(self, model: "Video2WorldModelRectifiedFlow", source_latent: torch.Tensor, ctx_cond, ctx_uncond,
+                 camera=None, *, num_conditional_frames: int = 1, guidance: float = 1.5, seed: int = 1,
+                 num_steps: int = 35, shift: float = 5.0, net_fn=None):
+        if model.config.sampler != "unipc":
+            raise ValueError(f"the camera sampler runs the rectified-flow UniPC loop, not {model.config.sampler!r}")
+        if model.config.use_kerras_sigma_at_inference:
+            raise ValueError("the camera sampler's schedule has no Karras sigmas "
+                             "(use_kerras_sigma_at_inference must be False)")
+        if source_latent.dim() != 5 or source_latent.shape[0] != 1:
+            raise ValueError(f"source_latent must be [1, C, T, H, W], got {tuple(source_latent.shape)}")
+        if net_fn is None and camera is None:
+            raise ValueError("the camera sampler needs `camera` (MinimalV1LVGDiT.prepare_camera)")
+        dev = model.device
+        _, C, Ts, H, W = source_latent.shape
+        x0 = source_latent.to(dev, torch.float32)
+        zeros = torch.zeros_like(x0)
+        noise = arch_invariant_rand((1, C, Ts, H, W), torch.float32, dev, seed)
+        super().__init__(model, torch.cat([zeros, x0, zeros], dim=2), ctx_cond, ctx_uncond,
+                         state_shape=(C, 3 * Ts, H, W), num_conditional_frames=num_conditional_frames,
+                         guidance=guidance, seed=seed, num_steps=num_steps, shift=shift, cfg_mode="video2world",
+                         net_fn=net_fn, init_noise=torch.cat([noise, x0, noise], dim=2),
+                         frame_mask=camera_frame_mask(3 * Ts, num_conditional_frames), camera=camera)
+
+    @torch.no_grad()
+    def target_latents(self):
+        """(target 0, target 1) latents, [1, C, T_seg, H, W] fp32 each."""
+        chunks = torch.chunk(self.latents(), 3, dim=2)
+        return chunks[0], chunks[2]
 
 
 class DistilledSamplingRun(_TokenState):

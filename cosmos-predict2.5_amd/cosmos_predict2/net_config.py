@@ -73,6 +73,11 @@ class DiTConfig:
     # (None = dense). The reference's dicts and lists are converted to that hashable form on construction.
     n_dense_blocks: int = -1
     natten_parameters: tuple = ()
+    # camera conditioning (CameraMiniTrainDIT, camera/networks/minimal_v4_dit_camera_conditioned.py): camera_dim > 0
+    # adds every block's cam_encoder = Linear(camera_dim, model_channels, bias=False) (:1079-1080), whose output is
+    # added to the self-attention's LN-modulated input (:1189-1194). 1536 = 6 Pluecker channels x the 16 x 16 pixels
+    # of one token (8x VAE, 2x patch): the class's cam_dim default.
+    camera_dim: int = 0
 
     def __post_init__(self):
         p = self.natten_parameters
@@ -227,6 +232,24 @@ NATTEN_720P_W12X24 = dict(window_size=(-1, 12, 24), stride=(1, 4, 8), base_size=
 DIT_2B_SPARSE_7DENSE = DIT_2B.replace(n_dense_blocks=7, natten_parameters=NATTEN_720P_W12X24)
 DIT_14B_SPARSE_9DENSE = DIT_14B.replace(n_dense_blocks=9, natten_parameters=NATTEN_720P_W12X24)
 
+# Camera-conditioned Video2World (paths under cosmos_predict2/_src/predict2/camera/). Net: hydra net
+# "cosmos_v1_2B_net_camera_conditioned" (configs/camera_conditioned/net.py:34-63, :105: CameraConditionedMinimalV1LVGDiT,
+# model_channels 2048, 16 heads, 28 blocks, no per-block absolute pos-emb, rope t 1.0 over the 7B dict's rope h / w 1.0),
+# selected by experiment multicamera_video2video_rectified_flow_2b_res_720_fps16
+# (configs/camera_conditioned/experiment/exp_2b.py:150-186), whose base is the rectified-flow experiment of
+# 2B/post-trained (:153, Stage-c_pt_4-Index-2-...-rf_with_edm_ckpt). That base's model.config.net dict overrides the /net
+# group default (configs/video2world/experiment/reason_embeddings/model_2B_reason_1p1_rectified_flow.py:312-325): RoPE
+# h / w 3.0, t 24 / 24 (:314-316), fps modulation off (:313), timestep_scale 0.001 (:317; the class default is 1.0,
+# networks/camera_conditioned_minimal_v1_lvg_dit.py:25), use_wan_fp32_strategy True (:324), crossattn projection 100352 ->
+# 1024 (:321-323). cam_dim is the block's default 1536 (networks/minimal_v4_dit_camera_conditioned.py:1025).
+# Sampler: the base experiment's conditional_frame_timestep 0.1 (specialized_model/SFT_2B_RF.py:766) reaches the inherited
+# denoise; its Karras flag does not show, because the camera model's own loop calls set_timesteps(num_steps, shift=shift)
+# without it (models/camera_conditioned_video2world_model_rectified_flow.py:301). state_t 24 is one of the three equal
+# segments [target 0 | source | target 1] the latent time axis holds (:296), CFG cond + g (cond - uncond) (:230).
+DIT_2B_CAMERA = DIT_2B.replace(camera_dim=1536)
+SAMPLER_CAMERA = SamplerConfig(use_kerras_sigma_at_inference=False, conditional_frame_timestep=0.1, state_t=24,
+                               cfg_mode="video2world", resolution="720")
+
 # model name (cosmos_predict2/config.py ModelKey.name) -> (net, sampler)
 MODELS = {
     "2B/post-trained": (DIT_2B, SAMPLER_2B_POST_TRAINED),
@@ -246,6 +269,9 @@ MODELS = {
     # 2.5 net post-trained with that sparsity, under the rectified-flow samplers of 2B/post-trained / 14B/pre-trained
     "2B/sparse-7dense": (DIT_2B_SPARSE_7DENSE, SAMPLER_2B_POST_TRAINED),
     "14B/sparse-9dense": (DIT_14B_SPARSE_9DENSE, SAMPLER_PRE_TRAINED),
+    # the reference registers the camera net and its rectified-flow experiment but ships no checkpoint key for it
+    # (the footing of "2B/distilled"): this entry serves a 2B net post-trained for camera control with that recipe
+    "2B/camera-cond": (DIT_2B_CAMERA, SAMPLER_CAMERA),
 }
 
 # Subset of VIDEO_RES_SIZE_INFO (cosmos_predict2/_src/predict2/datasets/utils.py:44-67); the model's

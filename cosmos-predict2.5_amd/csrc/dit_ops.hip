@@ -4,6 +4,8 @@
 //
 //   cp25_ln_mod          : [x' = x + gate*y]  ->  LayerNorm(x') * (1 + scale) + shift      (bf16)
 //                          minimal_v4_dit.py:1171-1179 (_fn), :1204 / :1237 / :1246 (gated residuals)
+//   cp25_ln_mod_cam      : the same with the camera net's per-token embedding added to h as one more bf16 op
+//                          (camera/networks/minimal_v4_dit_camera_conditioned.py:1189-1194)
 //   cp25_final_ln_mod    : fp32-autocast variant for the final layer                         (fp32 out)
 //                          minimal_v4_dit.py:974-991
 //   cp25_layer_norm      : affine LayerNorm (the cross-view net's layer_norm_cross_view_attn)    (bf16)
@@ -32,7 +34,10 @@ namespace {
 // FP8: h is emitted as the row-scaled fp8 operand of the next (fp8) GEMM instead of bf16: h8_out
 // [rows, D] OCP E4M3 and h_scale [rows] = max|h_row| / 448, the same definition as cp25_quant_fp8_rows
 // applied to the bf16 h (fp8_ops.hip), without the bf16 h round trip through HBM
-template <int NC, bool FP8 = false>  // NC = D / 512 chunks of 8 bf16 per lane
+// CAM: the camera-conditioned block's self-attention input `normalized_x + cam_emb` (minimal_v4_dit_camera_conditioned.py:
+// 1189-1194): h = bf16(h + cam[tok * cam_st + b * cam_sb + col]), one more bf16 tensor op on the rounded h, so one more
+// rounding; x', x_out and the statistics are those of the plain kernel. cam_sb = 0 shares the rows across the batch.
+template <int NC, bool FP8 = false, bool CAM = false>  // NC = D / 512 chunks of 8 bf16 per lane
 __global__ void __launch_bounds__(256) ln_mod_kernel(
     const unsigned short* __restrict__ x, int64_t x_st, int64_t x_sb,
     const unsigned short* __restrict__ y,  // optional residual branch output [tok, B, D]
@@ -40,7 +45,8 @@ __global__ void __launch_bounds__(256) ln_mod_kernel(
     const unsigned short* __restrict__ scale, int64_t mod_sb, int64_t mod_st,
     unsigned short* __restrict__ x_out, unsigned short* __restrict__ h_out, int64_t n_rows, int B,
     int64_t tok0, int64_t hw, float eps, unsigned char* __restrict__ h8_out = nullptr,
-    float* __restrict__ h_scale = nullptr) {
+    float* __restrict__ h_scale = nullptr, const unsigned short* __restrict__ cam = nullptr, int64_t cam_st = 0,
+    int64_t cam_sb = 0) {
   constexpr int D = NC * 512;
   const int lane = threadIdx.x & 63;
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -98,6 +104,8 @@ __global__ void __launch_bounds__(256) ln_mod_kernel(
     const int off = (c * 64 + lane) * 8;
     u16x8 sh = *reinterpret_cast<const u16x8*>(shift + mo + off);
     u16x8 sc = *reinterpret_cast<const u16x8*>(scale + mo + off);
+    u16x8 cm;
+    if constexpr (CAM) cm = *reinterpret_cast<const u16x8*>(cam + tok * cam_st + b * cam_sb + off);
     u16x8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -105,6 +113,7 @@ __global__ void __launch_bounds__(256) ln_mod_kernel(
       const float one_p = rbf(1.f + bf2f(sc[e]));           // (1 + scale)
       const float prod = rbf(ln * one_p);
       o[e] = f2bf(prod + bf2f(sh[e]));                      // + shift
+      if constexpr (CAM) o[e] = f2bf(bf2f(o[e]) + bf2f(cm[e]));  // + cam_emb (a separate bf16 op)
       if constexpr (FP8) v[c * 8 + e] = bf2f(o[e]);
     }
     if constexpr (!FP8) *reinterpret_cast<u16x8*>(h_out + row * D + off) = o;
@@ -425,11 +434,14 @@ inline bool mult8(std::initializer_list<int64_t> strides) {
   return (bits & 7) == 0;
 }
 
-template <bool FP8>
+template <bool FP8, bool CAM = false>
 int launch_ln_mod(const void* x, int64_t x_st, int64_t x_sb, const void* y, const void* gate, const void* shift,
                   const void* scale, int64_t mod_sb, int64_t mod_st, void* x_out, void* h_out, void* h8_out,
                   float* h_scale, int64_t n_tok, int B, int D, int64_t tok0, int64_t hw, float eps,
-                  hipStream_t stream) {
+                  hipStream_t stream, const void* cam = nullptr, int64_t cam_st = 0, int64_t cam_sb = 0) {
+  // the cam rows are read in 16-byte pieces: local token tok's row of batch entry b starts at tok cam_st + b cam_sb
+  if (CAM && (!cam || cam_st < D || cam_sb < 0 || !aligned16({cam}) || !mult8({cam_st, cam_sb})))
+    return CP25_ERR_INVAL;
   if (n_tok <= 0 || B <= 0 || hw <= 0 || !x || !shift || !scale) return CP25_ERR_INVAL;
   if (FP8 ? (!h8_out || !h_scale) : !h_out) return CP25_ERR_INVAL;
   if (y != nullptr && (gate == nullptr || x_out == nullptr)) return CP25_ERR_INVAL;
@@ -447,7 +459,8 @@ int launch_ln_mod(const void* x, int64_t x_st, int64_t x_sb, const void* y, cons
   auto* XO = (unsigned short*)x_out;
   auto* HO = (unsigned short*)h_out;
   auto* H8 = (unsigned char*)h8_out;
-#define LNM(NC) hipLaunchKernelGGL((ln_mod_kernel<NC, FP8>), grid, dim3(256), 0, stream, X, x_st, x_sb, Y, G, SH, SC, mod_sb, mod_st, XO, HO, rows, B, tok0, hw, eps, H8, h_scale)
+  auto* CM = (const unsigned short*)cam;
+#define LNM(NC) hipLaunchKernelGGL((ln_mod_kernel<NC, FP8, CAM>), grid, dim3(256), 0, stream, X, x_st, x_sb, Y, G, SH, SC, mod_sb, mod_st, XO, HO, rows, B, tok0, hw, eps, H8, h_scale, CM, cam_st, cam_sb)
   switch (D) {
     case 512: LNM(1); break;
     case 1024: LNM(2); break;
@@ -476,6 +489,23 @@ extern "C" int cp25_ln_mod_fp8(const void* x, int64_t x_st, int64_t x_sb, const 
                                float eps, hipStream_t stream) {
   return launch_ln_mod<true>(x, x_st, x_sb, y, gate, shift, scale, mod_sb, mod_st, x_out, nullptr, h8_out, h_scale,
                              n_tok, B, D, tok0, hw, eps, stream);
+}
+
+extern "C" int cp25_ln_mod_cam(const void* x, int64_t x_st, int64_t x_sb, const void* y, const void* gate,
+                               const void* shift, const void* scale, int64_t mod_sb, int64_t mod_st, const void* cam,
+                               int64_t cam_st, int64_t cam_sb, void* x_out, void* h_out, int64_t n_tok, int B, int D,
+                               int64_t tok0, int64_t hw, float eps, hipStream_t stream) {
+  return launch_ln_mod<false, true>(x, x_st, x_sb, y, gate, shift, scale, mod_sb, mod_st, x_out, h_out, nullptr,
+                                    nullptr, n_tok, B, D, tok0, hw, eps, stream, cam, cam_st, cam_sb);
+}
+
+extern "C" int cp25_ln_mod_cam_fp8(const void* x, int64_t x_st, int64_t x_sb, const void* y, const void* gate,
+                                   const void* shift, const void* scale, int64_t mod_sb, int64_t mod_st,
+                                   const void* cam, int64_t cam_st, int64_t cam_sb, void* x_out, void* h8_out,
+                                   float* h_scale, int64_t n_tok, int B, int D, int64_t tok0, int64_t hw, float eps,
+                                   hipStream_t stream) {
+  return launch_ln_mod<true, true>(x, x_st, x_sb, y, gate, shift, scale, mod_sb, mod_st, x_out, nullptr, h8_out,
+                                   h_scale, n_tok, B, D, tok0, hw, eps, stream, cam, cam_st, cam_sb);
 }
 
 extern "C" int cp25_final_ln_mod(const void* x, const void* y, const void* gate, int64_t gmod_sb, int64_t gmod_st,

@@ -253,6 +253,22 @@ int cp25_ln_mod_fp8(const void* x, int64_t x_st, int64_t x_sb, const void* y, co
                     const void* scale, int64_t mod_sb, int64_t mod_st, void* x_out, void* h8_out, float* h_scale,
                     int64_t n_tok, int B, int D, int64_t tok0, int64_t hw, float eps, hipStream_t stream);
 
+/* cp25_ln_mod / cp25_ln_mod_fp8 for the camera-conditioned net: the block's self-attention reads
+ * `normalized_x + cam_emb` (camera/networks/minimal_v4_dit_camera_conditioned.py:1189-1194), one more bf16 tensor op
+ * on the LN-modulated activation, so h = bf16(h_ln_mod + cam) with one more rounding than cp25_ln_mod; x', x_out, the
+ * statistics and every earlier rounding point are cp25_ln_mod's. cam: bf16, the row of local token tok and batch entry
+ * b at cam[tok * cam_st + b * cam_sb] (cam_sb = 0 shares one row across the batch; cam_st >= D, so a column view of a
+ * wider buffer is legal). cam 16-B aligned, cam_st and cam_sb multiples of 8, else CP25_ERR_INVAL. The fp8 form
+ * quantises that h per row (max|h| / 448), as cp25_ln_mod_fp8 does. */
+int cp25_ln_mod_cam(const void* x, int64_t x_st, int64_t x_sb, const void* y, const void* gate, const void* shift,
+                    const void* scale, int64_t mod_sb, int64_t mod_st, const void* cam, int64_t cam_st, int64_t cam_sb,
+                    void* x_out, void* h_out, int64_t n_tok, int B, int D, int64_t tok0, int64_t hw, float eps,
+                    hipStream_t stream);
+int cp25_ln_mod_cam_fp8(const void* x, int64_t x_st, int64_t x_sb, const void* y, const void* gate, const void* shift,
+                        const void* scale, int64_t mod_sb, int64_t mod_st, const void* cam, int64_t cam_st,
+                        int64_t cam_sb, void* x_out, void* h8_out, float* h_scale, int64_t n_tok, int B, int D,
+                        int64_t tok0, int64_t hw, float eps, hipStream_t stream);
+
 /* Final layer prologue under the reference's fp32 autocast: [x' = x + gate*y (bf16)], then
  * out = LayerNorm_fp32(x') * (1 + scale) + shift in fp32 (shift/scale fp32).
  * Replaces: FinalLayer.forward, minimal_v4_dit.py:974-991 (and the last block's MLP residual :1246). */
@@ -599,6 +615,18 @@ int cp25_u8_to_clip(const void* src, const int64_t* src_strides, int C, int T, i
  * unspecified. */
 int cp25_clip_to_u8(const void* src, const int64_t* src_strides, int T, int H, int W, int C, void* dst,
                     const int64_t* dst_strides, hipStream_t stream);
+
+/* ---------------------------------------------------------------- camera features
+ * Per-pixel Pluecker rays of one camera per latent frame, packed into the rows the camera-conditioned net's
+ * cam_encoder (Linear(1536, D), camera/networks/minimal_v4_dit_camera_conditioned.py:1080) multiplies.
+ * w2c [F, 3, 4] fp32 world-to-camera [R | t]; intrinsics [F, 4] fp32 (fx, fy, cx, cy) at the pixel size
+ * (16 Hp, 16 Wp); out [F * Hp * Wp, 1536] bf16 contiguous, token order (frame, hp, wp), feature order "(c m n)":
+ * c over [moment (3) | direction (3)], m / n the rows / columns of the token's 16 x 16 pixels. Per pixel centre
+ * (u + 0.5, v + 0.5): direction = unit(R^T K^-1 (u, v, 1)), moment = o x direction with o = -R^T t, in fp32 without
+ * contraction, rounded to bf16 once at the store. The ray arithmetic is get_plucker_rays
+ * (_src/imaginaire/modules/camera.py:172-236); the packing is this build's own (the reference ships none). */
+int cp25_plucker_tokens(const float* w2c, const float* intrinsics, void* out, int F, int Hp, int Wp,
+                        hipStream_t stream);
 
 #ifdef __cplusplus
 }
