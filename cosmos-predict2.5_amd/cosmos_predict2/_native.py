@@ -141,6 +141,7 @@ SIGNATURES = {
                             _I, _I, _I, _P],
     "cp25_u8_to_clip": [_P, c_int64_p, _I, _I, _I, _I, _P, _P],
     "cp25_clip_to_u8": [_P, c_int64_p, _I, _I, _I, _I, _P, c_int64_p, _P],
+    "cp25_lora_merge": [_P, _I64, _P, _P, _I64, _I64, _I, _F, _P],
 }
 
 
@@ -1229,3 +1230,37 @@ def clip_to_u8(clip: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
                              _stream(clip.device))
     _check("cp25_clip_to_u8", rc)
     return out
+
+
+# ----------------------------------------------------------------------------- LoRA
+LORA_MAX_RANK = 256
+
+
+def lora_merge(w: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float) -> torch.Tensor:
+    """cp25_lora_merge, in place: w[n, k] = bf16(float(w[n, k]) + (sum_j b[n, j] * a[j, k]) * scale) with the sum taken
+    in fp32 in ascending j, product and sum rounded separately. w is a 2-D bf16 view [N, K] with unit inner stride
+    (row stride >= K, e.g. a row slice of a fused q|k|v weight); a [r, K] and b [N, r] are contiguous fp32,
+    1 <= r <= 256; K % 8 == 0. Returns w."""
+    lib = load_library()
+    if w.dtype != torch.bfloat16 or w.dim() != 2 or w.stride(1) != 1:
+        raise ValueError("lora_merge: w must be a 2-D bf16 view with a contiguous last dim")
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError(f"lora_merge: a and b must be float32 (got {a.dtype}, {b.dtype}); convert bf16 adapters with "
+                         ".float(), which is exact")
+    n, k = w.shape
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != k or b.shape[0] != n or a.shape[0] != b.shape[1]:
+        raise ValueError(f"lora_merge: a {tuple(a.shape)} / b {tuple(b.shape)} do not fit w {tuple(w.shape)} as "
+                         "[r, K] / [N, r]")
+    r = a.shape[0]
+    if not 1 <= r <= LORA_MAX_RANK:
+        raise ValueError(f"lora_merge: rank {r} outside [1, {LORA_MAX_RANK}]")
+    if not a.is_contiguous() or not b.is_contiguous():
+        raise ValueError("lora_merge: a and b must be contiguous")
+    if a.device != w.device or b.device != w.device:
+        raise ValueError("lora_merge: w, a and b must be on one device")
+    if n == 0:
+        return w
+    rc = lib.cp25_lora_merge(_ptr(w), w.stride(0) if n > 1 else max(w.stride(0), k), _ptr(a), _ptr(b), n, k, r,
+                             float(scale), _stream(w.device))
+    _check("cp25_lora_merge", rc)
+    return w

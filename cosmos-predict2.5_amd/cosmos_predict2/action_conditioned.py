@@ -122,6 +122,8 @@ class ActionConditionedInference:
     """The reference's action-conditioned `inference()` chunk loop over one trajectory."""
 
     def __init__(self, pipe: Optional[Video2WorldInference] = None, **pipe_kwargs):
+        """pipe_kwargs go to Video2WorldInference (ckpt_path, tokenizer_path, lora_path / lora_alpha / lora_scale for a
+        LoRA post-trained net, ...)."""
         self.pipe = pipe or Video2WorldInference("2B/robot/action-cond", **pipe_kwargs)
 
     @torch.no_grad()

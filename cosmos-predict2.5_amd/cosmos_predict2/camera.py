@@ -149,7 +149,9 @@ class CameraInference:
                 raise ValueError("a camera-conditioned net combined with context parallelism is not built")
             pipe = Video2WorldInference(setup.model, ckpt_path=setup.checkpoint_path,
                                         tokenizer_path=setup.tokenizer_path, state_t=setup.state_t,
-                                        text_encoder=text_encoder, pixel_path=setup.pixel_path, **pipe_kwargs)
+                                        text_encoder=text_encoder, pixel_path=setup.pixel_path,
+                                        lora_path=setup.lora_path, lora_alpha=setup.lora_alpha,
+                                        lora_scale=setup.lora_scale, **pipe_kwargs)
         self.pipe = pipe
         if not pipe.model.net_cfg.camera_dim:
             raise ValueError(f"CameraInference needs a camera-conditioned net (model {MODEL_NAME!r}), got "

@@ -73,6 +73,12 @@ class SetupArguments(pydantic.BaseModel):
     # build-specific, like state_t (the reference has no such field): "host" resizes, normalises and quantises pixels
     # with torch on the CPU / in fp32; "device" keeps them uint8 on the GPU (cosmos_predict2/pixels.py)
     pixel_path: Literal["host", "device"] = "host"
+    # LoRA post-training (the reference's use_lora / lora_rank / lora_alpha recipe): an adapter-only file (safetensors or
+    # .pt) merged into the checkpoint's weights at load; lora_alpha None means alpha = the adapter's rank (32 / 32 in
+    # the shipped recipe). alpha and scale also apply to a checkpoint_path that is itself in peft's layout
+    lora_path: Optional[str] = None
+    lora_alpha: Optional[float] = None
+    lora_scale: float = 1.0
 
     @pydantic.model_validator(mode="before")
     @classmethod
@@ -82,7 +88,7 @@ class SetupArguments(pydantic.BaseModel):
                 raise ValueError(f"unknown model {data.get('model')}")
             if data.get("context_parallel_size") is None:
                 data["context_parallel_size"] = int(os.environ.get("WORLD_SIZE", "1"))
-            for k in ("checkpoint_path", "tokenizer_path"):
+            for k in ("checkpoint_path", "tokenizer_path", "lora_path"):
                 if data.get(k) is not None and not os.path.exists(data[k]):
                     raise ValueError(f"{k} '{data[k]}' does not exist.")
         return data

@@ -24,6 +24,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _native as N
+from .checkpoint import LoraAdapters, split_lora_state_dict
 from .context_parallel import all_gather_into_async, kv_chunk_views, run_lanes
 from .net_config import DiTConfig
 from .sparse_attn import PlanCache, sparse_block_params
@@ -315,6 +316,9 @@ class MinimalV1LVGDiT:
         # with row-scaled activations and per-output-channel weight scales (config 5, see set_linear_precision)
         self.linear_precision = "bf16"
         self._fp8_w: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        # one entry per merged LoRA adapter (load_state_dict of a peft-layout dict, merge_lora): modules, rank, alpha, scale
+        self.lora_info: List[dict] = []
+        self._borrowed: set = set()
         # True: self-attention q rounded to bf16 exactly where the reference rounds it (the scale goes
         # on the fp32 scores); False (default): q * scale * log2(e) rounded once (see _self_attn_mode)
         self.exact_q_rounding = False
@@ -549,9 +553,15 @@ class MinimalV1LVGDiT:
         return N.gemm_fp8(q, s, w8, ws)
 
     # ---------------------------------------------------------------- loading
-    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True) -> None:
+    def load_state_dict(self, state_dict: Dict[str, torch.Tensor], strict: bool = True,
+                        lora_alpha: Optional[float] = None, lora_scale: float = 1.0) -> None:
         """Accepts the reference's checkpoint dict (`net.` prefix optional, `_extra_state` skipped,
-        model_loader.py:173-174; text2world_model_rectified_flow.py:775-783)."""
+        model_loader.py:173-174; text2world_model_rectified_flow.py:775-783), plain or in peft's LoRA layout
+        (`base_layer.` keys plus lora_A / lora_B tensors, checkpoint.split_lora_state_dict): the adapters are merged
+        into their own bf16 weights on the device (cp25_lora_merge, scale = lora_scale * alpha / r, lora_alpha None:
+        alpha = r) before any fused or fp32 copy is built, then freed. Adapters that cannot be merged raise, at
+        strict=False too. See merge_lora for the arithmetic and for an adapter-only file over a loaded net."""
+        state_dict, adapters = split_lora_state_dict(state_dict)
         shapes = state_dict_shapes(self.cfg)
         sd = {}
         for k, v in state_dict.items():
@@ -568,8 +578,12 @@ class MinimalV1LVGDiT:
         cfg = self.cfg
         dev = self.device
         self.sd = {k: v.to(device=dev, dtype=shapes[k][1]).contiguous() for k, v in sd.items()}
-        self._x_embed_w128 = None
-        self._fp8_w = {}
+        # tensors that already had the device and dtype are the caller's own: an in-place merge copies them first
+        self._borrowed = {k for k, v in sd.items() if self.sd[k] is v}
+        self.lora_info = []
+        if adapters:  # into the unfused bf16 tensors, ahead of every derived copy
+            self._merge_adapters(adapters, lora_alpha, lora_scale, fused=False)
+            del adapters
         D = cfg.model_channels
         p = self.sd
         # fused / stacked views used by the hot path
@@ -578,6 +592,99 @@ class MinimalV1LVGDiT:
         for i in range(cfg.num_blocks):
             for n in "qkv":
                 del p[f"blocks.{i}.self_attn.{n}_proj.weight"]  # keep only the fused copy in HBM
+        if cfg.cross_view_attn_map:  # the cross-view q|k|v projections as one [3D, D] GEMM per block
+            self.w_cv_qkv = [torch.cat([p[f"blocks.{i}.cross_view_attn.{m}_proj.weight"] for m in "qkv"], 0).contiguous()
+                             for i in range(cfg.num_blocks)]
+        self._build_derived()
+        if D % 512:
+            raise ValueError("model_channels must be a multiple of 512")
+
+    def _lora_weight(self, module: str, fused: bool, write: bool = False) -> torch.Tensor:
+        """The bf16 tensor (or row slice of a fused copy) that holds `<module>.weight`; write=True: to be changed in
+        place, so a tensor still shared with the caller's state dict is copied first. KeyError for a module the net
+        does not have as a 2-D weight, or whose base weight is not loaded."""
+        key = module + ".weight"
+        shape = state_dict_shapes(self.cfg).get(key)
+        if shape is None or len(shape[0]) != 2:
+            raise KeyError(f"LoRA adapter for {module!r}: this net has no 2-D weight {key!r}")
+        if key in self.sd:
+            if write and key in self._borrowed:
+                self.sd[key] = self.sd[key].clone()
+                self._borrowed.discard(key)
+            return self.sd[key]
+        parts = module.split(".")  # blocks.<i>.self_attn.<n>_proj lives only in the fused q|k|v copy once loaded
+        if fused and len(parts) == 4 and parts[2] == "self_attn" and parts[3] in ("q_proj", "k_proj", "v_proj"):
+            D = self.cfg.model_channels
+            j = "qkv".index(parts[3][0])
+            return self.w_qkv[int(parts[1])][j * D:(j + 1) * D]
+        raise KeyError(f"LoRA adapter for {module!r}: its base weight {key!r} is not loaded")
+
+    def _merge_adapters(self, adapters: LoraAdapters, alpha: Optional[float], scale: float, fused: bool) -> None:
+        """Checks every adapter, then merges each into its bf16 weight (cp25_lora_merge) and records the call in
+        lora_info. Nothing is merged if any adapter fails its check."""
+        jobs = []
+        for module, (a, b) in adapters.items():
+            w = self._lora_weight(module, fused)
+            n, k = w.shape
+            if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1] or a.shape[1] != k or b.shape[0] != n:
+                raise ValueError(f"LoRA adapter for {module!r}: lora_A {tuple(a.shape)} / lora_B {tuple(b.shape)} do "
+                                 f"not fit the [{n}, {k}] weight as [r, {k}] / [{n}, r]")
+            r = a.shape[0]
+            if not 1 <= r <= N.LORA_MAX_RANK:
+                raise ValueError(f"LoRA adapter for {module!r}: rank {r} outside [1, {N.LORA_MAX_RANK}]")
+            if not (a.is_floating_point() and b.is_floating_point()):
+                raise ValueError(f"LoRA adapter for {module!r}: lora_A / lora_B must be floating point")
+            if k % 8:
+                raise ValueError(f"LoRA adapter for {module!r}: cp25_lora_merge needs K % 8 == 0, the weight has K = {k}")
+            al = float(r if alpha is None else alpha)
+            jobs.append((module, a, b, r, al, float(scale) * al / r))  # the scale in double; fp32 at the call
+        for module, a, b, r, al, sc in jobs:
+            N.lora_merge(self._lora_weight(module, fused, write=True), a.to(device=self.device, dtype=F32).contiguous(),
+                         b.to(device=self.device, dtype=F32).contiguous(), sc)
+
+        def one(vals):
+            vals = sorted(set(vals))
+            return vals[0] if len(vals) == 1 else vals
+
+        self.lora_info.append({"modules": len(jobs), "rank": one(j[3] for j in jobs), "alpha": one(j[4] for j in jobs),
+                               "scale": one(torch.tensor(j[5], dtype=F32).item() for j in jobs)})
+
+    def merge_lora(self, adapters: LoraAdapters, alpha: Optional[float] = None, scale: float = 1.0) -> None:
+        """Merges a LoRA adapter {module: (lora_A [r, K], lora_B [N, r])} (checkpoint.split_lora_state_dict /
+        load_lora_adapters) into the loaded weights, in place and for good: W <- bf16(W + (B A) * s) per target, s =
+        fp32(scale * alpha / r) with alpha = r when None (the recipe's 32 / 32), B A summed in fp32 in ascending rank
+        order and one bf16 rounding (cp25_lora_merge). The bits equal those of load_state_dict on the peft-layout dict
+        of the same base and adapter: q, k and v targets are merged into their row slices of the fused q|k|v weights,
+        and the fp32 and padded copies, the fp8 weight cache and the bias / embedding caches are rebuilt or cleared as
+        load_state_dict does. Targets are the modules the dict names (the recipe's q_proj, k_proj, v_proj,
+        output_proj, mlp.layer1, mlp.layer2 of self_attn / cross_attn / cross_view_attn, or any other 2-D weight);
+        KeyError for a module this net lacks, ValueError for shapes that do not fit. Nothing is merged if one fails.
+
+        A ContextCache (prepare_context) or CameraCache (prepare_camera) made before the call holds projections of
+        the old weights and is stale: make them again. There is no un-merge; reload the base to drop an adapter.
+        Calling this twice stacks two adapters, which is legal; because each merge rounds to bf16, the result
+        depends on the order of the calls at rounding level."""
+        if not self.sd:
+            raise RuntimeError("merge_lora needs a loaded net: call load_state_dict first")
+        if not adapters:
+            raise ValueError("merge_lora: the adapter dict is empty")
+        self._merge_adapters(adapters, alpha, scale, fused=True)
+        if self.cfg.cross_view_attn_map:  # refresh the fused cross-view copy from its merged sources
+            D = self.cfg.model_channels
+            for module in adapters:
+                parts = module.split(".")
+                if len(parts) == 4 and parts[2] == "cross_view_attn" and parts[3] in ("q_proj", "k_proj", "v_proj"):
+                    j = "qkv".index(parts[3][0])
+                    self.w_cv_qkv[int(parts[1])][j * D:(j + 1) * D].copy_(self.sd[module + ".weight"])
+        self._build_derived()
+
+    def _build_derived(self) -> None:
+        """The fp32 and padded copies of the bf16 weights in self.sd, and every weight-derived cache reset: what has
+        to follow any change of the weights (load_state_dict, merge_lora)."""
+        cfg, dev, p = self.cfg, self.device, self.sd
+        D = cfg.model_channels
+        self._x_embed_w128 = None
+        self._fp8_w = {}
         self.w_ada1 = torch.cat([p[f"blocks.{i}.adaln_modulation_{m}.1.weight"]
                                  for i in range(cfg.num_blocks) for m in ("self_attn", "cross_attn", "mlp")], 0).float()
         self.w_ada2 = torch.stack([p[f"blocks.{i}.adaln_modulation_{m}.2.weight"]
@@ -592,9 +699,6 @@ class MinimalV1LVGDiT:
         self.w_t2 = p["t_embedder.1.linear_2.weight"].float()
         self.w_f1 = p["final_layer.adaln_modulation.1.weight"].float()
         self.w_f2 = p["final_layer.adaln_modulation.2.weight"].float()
-        if cfg.cross_view_attn_map:  # the cross-view q|k|v projections as one [3D, D] GEMM per block
-            self.w_cv_qkv = [torch.cat([p[f"blocks.{i}.cross_view_attn.{m}_proj.weight"] for m in "qkv"], 0).contiguous()
-                             for i in range(cfg.num_blocks)]
         if cfg.adaln_view_embedding:
             self.w_view_proj = p["adaln_view_proj.weight"].float()
             self.b_view_proj = p["adaln_view_proj.bias"].float()
@@ -602,8 +706,6 @@ class MinimalV1LVGDiT:
         self._embed_f32 = None  # multi-view patch embedding: fp32 weights padded to K % 32 == 0, view-channel fold
         self.refresh_norm_bounds()
         self._rope_cache.clear()
-        if D % 512:
-            raise ValueError("model_channels must be a multiple of 512")
 
     def refresh_norm_bounds(self) -> None:
         """Per-block (max|q|, max|k|) bounds for the attention softmax shift: the q/k RMSNorm (minimal_v4_dit.py:355-358)

@@ -36,7 +36,8 @@ class Inference:
         self.pipe = Video2WorldInference(args.model, ckpt_path=args.checkpoint_path, tokenizer_path=args.tokenizer_path,
                                          context_parallel_size=args.context_parallel_size or 1,
                                          state_t=args.state_t, text_encoder=text_encoder,
-                                         pixel_path=args.pixel_path)
+                                         pixel_path=args.pixel_path, lora_path=args.lora_path,
+                                         lora_alpha=args.lora_alpha, lora_scale=args.lora_scale)
         if self.rank0:
             Path(args.output_dir).mkdir(parents=True, exist_ok=True)
 

@@ -33,7 +33,7 @@ class ActionStreamingInference:
     def __init__(self, text_embeddings: torch.Tensor, pipe: Optional[Video2WorldInference] = None, **pipe_kwargs):
         """text_embeddings: [Lctx, dim] or [1, Lctx, dim], what the net's text context takes (the empty-string
         embedding in the reference). pipe_kwargs go to Video2WorldInference (ckpt_path, tokenizer_path, pixel_path,
-        net_cfg / sampler_cfg overrides, ...)."""
+        lora_path / lora_alpha / lora_scale for a LoRA post-trained student, net_cfg / sampler_cfg overrides, ...)."""
         self.pipe = pipe or Video2WorldInference(MODEL_NAME, **pipe_kwargs)
         if self.pipe.model.config.sampler != "dmd2_stream":
             raise ValueError("ActionStreamingInference needs a streaming ('dmd2_stream') model")

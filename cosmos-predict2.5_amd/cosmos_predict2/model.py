@@ -73,8 +73,10 @@ class Video2WorldModelRectifiedFlow:
         self.pixel_path = "host"
 
     # ------------------------------------------------------------------ plumbing
-    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
-        self.net.load_state_dict(sd, strict=strict)
+    def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True, lora_alpha: Optional[float] = None,
+                        lora_scale: float = 1.0):
+        """A plain or peft-LoRA-layout checkpoint dict (MinimalV1LVGDiT.load_state_dict merges the adapters)."""
+        self.net.load_state_dict(sd, strict=strict, lora_alpha=lora_alpha, lora_scale=lora_scale)
 
     def set_context_parallel_group(self, group) -> None:
         self.cp_group = group

@@ -26,6 +26,8 @@ class MultiviewInference:
     """`generate(views, prompt, ...)` -> [1, 3, V*T, H, W] (stack_mode "time") or [1, 3, T, V*H, W]."""
 
     def __init__(self, pipe: Optional[Video2WorldInference] = None, **pipe_kwargs):
+        """pipe_kwargs go to Video2WorldInference (ckpt_path, tokenizer_path, lora_path / lora_alpha / lora_scale for a
+        LoRA post-trained net: cross_view_attn projections are adapter targets like self_attn's, ...)."""
         pipe_kwargs.setdefault("model_name", "2B/auto/multiview")
         self.pipe = pipe or Video2WorldInference(**pipe_kwargs)
 

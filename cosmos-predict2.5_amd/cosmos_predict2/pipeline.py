@@ -110,12 +110,17 @@ class Video2WorldInference:
                  state_t: Optional[int] = None, text_encoder: Optional[Callable] = None,
                  net_cfg: Optional[DiTConfig] = None, sampler_cfg: Optional[SamplerConfig] = None,
                  weights_seed: int = 0, linear_precision: str = "bf16", attention_precision: str = "bf16",
-                 pixel_path: str = "host"):
+                 pixel_path: str = "host", lora_path: Optional[str] = None, lora_alpha: Optional[float] = None,
+                 lora_scale: float = 1.0):
         """linear_precision: "bf16" (the reference's arithmetic) or "fp8" (the DiT block GEMMs as fp8
         MFMA, config 5's option; MinimalV1LVGDiT.set_linear_precision). attention_precision: "bf16", "fp8qk"
         (self-attention Q K^T on e4m3) or "fp8" (also P.V; MinimalV1LVGDiT.set_attention_precision).
         pixel_path: "host" (resize, normalisation and output quantisation as torch ops, on the CPU / in fp32) or
-        "device" (uint8 pixels stay on the GPU: cosmos_predict2/pixels.py; enables return_uint8=True)."""
+        "device" (uint8 pixels stay on the GPU: cosmos_predict2/pixels.py; enables return_uint8=True).
+        lora_path: an adapter-only LoRA file (safetensors or .pt: lora_A / lora_B tensors) merged into the loaded
+        weights once, on the device (MinimalV1LVGDiT.merge_lora); lora_alpha (None: the adapter's rank, the recipe's
+        32 / 32) and lora_scale (1.0) set its strength, scale = lora_scale * alpha / r. They apply as well to a
+        ckpt_path that is itself in peft's layout (base_layer. keys plus adapters), which needs no lora_path."""
         if pixel_path not in ("host", "device"):
             raise ValueError(f"pixel_path must be 'host' or 'device', got {pixel_path!r}")
         self.pixel_path = pixel_path
@@ -147,8 +152,12 @@ class Video2WorldInference:
             sd = load_dit_checkpoint(ckpt_path)
         else:
             sd = init_state_dict(ncfg, seed=weights_seed, device=self.device)
-        self.model.load_state_dict(sd)
+        self.model.load_state_dict(sd, lora_alpha=lora_alpha, lora_scale=lora_scale)
         del sd
+        if lora_path is not None:
+            from .checkpoint import load_lora_adapters
+
+            self.model.net.merge_lora(load_lora_adapters(lora_path), alpha=lora_alpha, scale=lora_scale)
         self.model.pixel_path = pixel_path
         self.model.net.set_linear_precision(linear_precision)
         self.model.net.set_attention_precision(attention_precision)

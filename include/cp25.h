@@ -628,6 +628,23 @@ int cp25_clip_to_u8(const void* src, const int64_t* src_strides, int T, int H, i
 int cp25_plucker_tokens(const float* w2c, const float* intrinsics, void* out, int F, int Hp, int Wp,
                         hipStream_t stream);
 
+/* ---------------------------------------------------------------- LoRA adapter merge (lora_ops.hip)
+ * Folds one peft LoRA adapter into a bf16 weight, in place, once at load time: the reference injects adapters into
+ * q_proj, k_proj, v_proj, output_proj, mlp.layer1 and mlp.layer2 (add_lora, text2world_model_rectified_flow.py:923-1008;
+ * rank 32, alpha 32 by default, :92-96), keeps the LoRA parameters in fp32 (:1004) and loads checkpoints whose base
+ * weights sit under `base_layer.` keys (utils/model_loader.py:134-169). It runs them unmerged,
+ * base(x) + B(A x) * scale; this build merges, so every GEMM and fused epilogue of the hot path is unchanged.
+ *
+ * w: bf16 view [n_rows, k_cols] with leading dimension ldw >= k_cols (elements), e.g. the k rows of a fused q|k|v
+ * weight. a [rank, k_cols] and b [n_rows, rank] fp32 contiguous. Per element, in fp32 without contraction:
+ *   acc = 0; for j = 0 .. rank - 1 ascending: acc = acc + (b[n, j] * a[j, k])       (product and sum each rounded)
+ *   w[n, k] = bf16_rne(float(w[n, k]) + acc * scale)                                (one product, one sum, one rounding)
+ * so the result equals the same sequence of fp32 torch ops bit for bit. 1 <= rank <= 256; k_cols % 8 == 0, ldw % 8 == 0,
+ * w and a 16-B aligned; -22 otherwise. Any n_rows. Each element is read and written by one lane; rows outside the view
+ * and columns [k_cols, ldw) are never touched. No atomics, no workspace. */
+int cp25_lora_merge(void* w, int64_t ldw, const float* a, const float* b, int64_t n_rows, int64_t k_cols, int rank,
+                    float scale, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
