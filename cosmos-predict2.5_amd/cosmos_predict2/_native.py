@@ -130,6 +130,7 @@ SIGNATURES = {
     "cp25_rms_norm_silu": [_P, _P, _P, _I64, _I, _I, _P],
     "cp25_conv3d_select": [_I],
     "cp25_attn_cross_select": [_I],
+    "cp25_attn_self_select": [_I],
     "cp25_softmax_rows": [_P, _I64, _I, _I64, _F, _P, _I64, _P],
     "cp25_vae_attn": [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I, _I, _I, _I, _F, _P, _I64,
                       _P],
@@ -454,17 +455,11 @@ def attn_cross_select(form: int) -> int:
 
 
 def attn_self_select(form: int) -> int:
-    """Lab builds only (tools/lab/w64/build_lab.sh, loaded through _LIB_PATH): cp25_attn_self_select, the kernel form
-    of prescaled bf16 self-attention launches, 0 = attn_fwd_m16 (the product kernel), 1 = attn_fwd_w64 in the zero- and
-    fixed-shift modes, 2 = attn_fwd_w64 in every mode (bit-identical). Returns the previous form."""
-    lib = load_library()
-    fn = getattr(lib, "cp25_attn_self_select", None)
-    if fn is None:
-        raise RuntimeError("cp25_attn_self_select: not in this libcp25.so (attn_fwd_w64 is a lab build, "
-                           "tools/lab/w64/build_lab.sh)")
-    fn.argtypes = [ctypes.c_int]
-    fn.restype = ctypes.c_int
-    rc = fn(int(form))
+    """cp25_attn_self_select: the kernel form of long-key (Lk > 4096) prescaled bf16 self-attention launches in the
+    fixed-shift mode, 1 = the library's routing (default: attn_fwd_wq, 384 query rows per workgroup, 320 up to 8192 keys),
+    0 = attn_fwd_m16 everywhere, 320 / 384 = that width of attn_fwd_wq wherever it supports the launch (A/B and tests;
+    bit-identical per row). Returns the previous form."""
+    rc = load_library().cp25_attn_self_select(int(form))
     _check("cp25_attn_self_select", min(rc, 0))
     return rc
 

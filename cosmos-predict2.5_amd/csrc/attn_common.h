@@ -1,5 +1,5 @@
 // Pieces shared by the self/cross-attention kernels (attn_fwd.hip: attn_fwd_m16, attn_fwd_f8, the host launch;
-// attn_w64.hip: attn_fwd_w64): the argument block, the tile geometry and the small device helpers.
+// attn_wide.hip: attn_fwd_wq): the argument block, the tile geometry and the small device helpers.
 #pragma once
 #include "cp25_common.h"
 
@@ -129,10 +129,10 @@ constexpr int kKBuf16 = kKBlk * kKStride16;        // 18432
 constexpr int kVBuf16 = kKBlk * kVStride16;        // 18432
 constexpr int kLds16 = 2 * kKBuf16 + 2 * kVBuf16;  // 73728
 
-// attn_fwd_w64 (attn_w64.hip): the kernel for a softmax mode (0 fixed, 1 zero shift, 2 online max) and symbol (tail
-// segments separate in profiles)
+// attn_fwd_wq (attn_wide.hip): the kernel for a workgroup of `rows` query rows (320 or 384), a softmax mode (0 fixed,
+// 1 zero shift) and symbol (tail segments separate in profiles); nullptr where that form is not built
 typedef void (*AttnKernel)(AttnArgs);
-AttnKernel w64_kernel(int mode, bool tail);
-constexpr int kW64Threads = 256;  // 4 waves, one per SIMD
+AttnKernel wq_kernel(int rows, int mode, bool tail);
+constexpr int kWqThreads = 256;  // 4 waves, one per SIMD
 
 }  // namespace cp25attn

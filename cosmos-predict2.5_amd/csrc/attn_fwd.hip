@@ -4,7 +4,9 @@
 // (q/k/v recast to bf16, softmax(QK^T / sqrt(D)) V, no mask, no dropout, non-causal), which the DiT
 // calls through MinimalA2AAttnOp (networks/a2a_cp.py:208-219) on [B, S, H, D] tensors.
 //
-// Two kernels:
+// Three kernels:
+//   attn_fwd_wq   (attn_wide.hip, round 13) long-key self-attention launches in the fixed-shift mode: one wave per SIMD,
+//                 320 / 384 query rows per workgroup, bit-identical per row to attn_fwd_m16 (routing: wide_rows below).
 //   attn_fwd_m16  every bf16 form. 8 waves x 32 query rows of one (b, h) per workgroup, v_mfma_f32_16x16x32_bf16,
 //                 ping-pong of the two waves of a SIMD (one runs its MFMA phase while the other runs its softmax),
 //                 K/V 64-key tiles double-buffered in padded LDS rows, counted-lgkmcnt operand ring, row sums by
@@ -1299,8 +1301,8 @@ double split_cost(int64_t nwg, int64_t ntiles, int s, int64_t rows, int64_t cus)
 // the segments; returns their count (0: no tail split), the largest segment's workspace in *ws_need.
 struct TailSeg { int bh, qb_lo, nblk, s; };
 constexpr int kMaxTailSegs = 4;
-int plan_tail(int B, int H, int Lq, int Lk, TailSeg* seg, size_t* ws_need, double* saved) {
-  const int64_t nqb = cdiv(Lq, kQBlk), ntiles = cdiv(Lk, kKBlk);
+int plan_tail(int B, int H, int Lq, int Lk, int qblk, TailSeg* seg, size_t* ws_need, double* saved) {
+  const int64_t nqb = cdiv(Lq, qblk), ntiles = cdiv(Lk, kKBlk);
   const int64_t nwg = nqb * B * H, cus = num_cus();
   const int64_t r = nwg % cus;
   *ws_need = 0;
@@ -1313,13 +1315,26 @@ int plan_tail(int B, int H, int Lq, int Lk, TailSeg* seg, size_t* ws_need, doubl
     const int bh = (int)(t / nqb), qb = (int)(t % nqb);
     const int nblk = (int)std::min<int64_t>(nqb - qb, nwg - t);
     if (n == kMaxTailSegs) return 0;
+    const int64_t rows = std::min<int64_t>(Lq, (int64_t)(qb + nblk) * qblk) - (int64_t)qb * qblk;
     int s = 1;
     for (int c = 2; c <= 8 && c <= ntiles; ++c) {  // the most splits that still fit one round
       const int64_t tps = cdiv(ntiles, c);
       if (cdiv(ntiles, tps) == c && (int64_t)nblk * c <= cus) s = c;
     }
+    if (s == 1 && qblk != kQBlk) {
+      // attn_fwd_wq (round 13): a segment too long for one round of splits (the metric launch's last round is 160
+      // workgroups of one (b, h) at either width) runs as the split count whose rounds of shorter workgroups cost the
+      // least (160 x 3 = 480 workgroups: two rounds of a third each). attn_fwd_m16's launches keep the one-round rule,
+      // so their plans, and with them which rows are merged partials, are what they were.
+      double best = 1e300;
+      for (int c = 2; c <= 8 && c <= ntiles; ++c) {
+        const int64_t tps = cdiv(ntiles, c);
+        if (cdiv(ntiles, tps) != c) continue;
+        const double cc = split_cost(nblk, ntiles, c, rows, cus);
+        if (cc < best) { best = cc; s = c; }
+      }
+    }
     if (s == 1) return 0;
-    const int64_t rows = std::min<int64_t>(Lq, (int64_t)(qb + nblk) * kQBlk) - (int64_t)qb * kQBlk;
     seg[n++] = TailSeg{bh, qb, nblk, s};
     cost += split_cost(nblk, ntiles, s, rows, cus) + 8.0;  // + launch overhead of the split and merge kernels
     need = std::max<size_t>(need, (size_t)s * rows * (kD + 1) * sizeof(float));
@@ -1327,13 +1342,15 @@ int plan_tail(int B, int H, int Lq, int Lk, TailSeg* seg, size_t* ws_need, doubl
   }
   const double unsplit = (double)(ntiles + 44);  // the tail round as one round of whole workgroups
   if (cost >= 0.9 * unsplit) return 0;
+  // the multi-round segments above: only where the model recovers at least 0.5 % of the launch
+  if (qblk != kQBlk && unsplit - cost < 0.005 * (double)cdiv(nwg, cus) * unsplit) return 0;
   *ws_need = need;
   if (saved) *saved = unsplit - cost;
   return n;
 }
 
-int plan_split(int B, int H, int Lq, int Lk) {
-  const int64_t nqb = cdiv(Lq, kQBlk), ntiles = cdiv(Lk, kKBlk);
+int plan_split(int B, int H, int Lq, int Lk, int qblk) {
+  const int64_t nqb = cdiv(Lq, qblk), ntiles = cdiv(Lk, kKBlk);
   const int64_t nwg = nqb * B * H, cus = num_cus();
   const int64_t rows = (int64_t)B * H * Lq;
   int best = 1;
@@ -1346,7 +1363,7 @@ int plan_split(int B, int H, int Lq, int Lk) {
       TailSeg seg[kMaxTailSegs];
       size_t need;
       double saved;
-      if (plan_tail(B, H, Lq, Lk, seg, &need, &saved) > 0) cost -= saved;
+      if (plan_tail(B, H, Lq, Lk, qblk, seg, &need, &saved) > 0) cost -= saved;
     }
     if (cost < best_cost * 0.995) { best_cost = cost; best = s; }
   }
@@ -1378,18 +1395,24 @@ bool m16_gated(float q_norm_bound, float k_norm_bound, bool long_keys) {
 // per block. Set only through cp25_attn_cross_select (never read from the environment).
 int g_xattn_form = 1;
 
-#ifdef CP25_LAB_W64
-// Lab build only (tools/lab/w64/build_lab.sh): attn_fwd_w64, one wave per SIMD owning 64 query rows,
-// for prescaled self-attention launches (Lk > 4096, bf16, not the gated pair): g_self_form 1 = w64 in the zero- and
-// fixed-shift modes, 2 = w64 in every mode, 0 = attn_fwd_m16 (the product kernel) in every mode. Bit-identical to
-// attn_fwd_m16; measured 0.6 % slower inside the DiT (2.4 % with trained-size norm weights), so not in the product.
+// Long-key self-attention launches (round 13): attn_fwd_wq (attn_wide.hip), one wave per SIMD and
+// 320 or 384 query rows per workgroup, for prescaled, ungated bf16 launches with Lk > 4096 in the fixed-shift mode (the
+// mode of every long-key launch with usable bounds); bit-identical per row to attn_fwd_m16. g_self_form: 0 =
+// attn_fwd_m16 everywhere, 1 = the library's routing (wq_default_rows), 320 / 384 = that width wherever attn_fwd_wq
+// supports the launch. Set only through cp25_attn_self_select (never read from the environment). The routing depends
+// only on what cp25_attn_kernel is given, so the name it reports is the kernel that runs.
+// The library's width: 384 rows, measured -7.4 % per launch against attn_fwd_m16 at the metric launch (320: -5.0 %)
+// and -8.8 % at a CP = 8 rank's 13 640 x 109 120 (320: -5.5 %); up to 8192 keys 320 rows, which at config 5's
+// L = 4800 measured -15 % against -6 % for 384 (its 480 shorter workgroups fill the second round better than 416
+// longer ones). profiles/r13/attn_wide/SUMMARY.md.
+int wq_default_rows(int Lk) { return Lk > 8192 ? 384 : 320; }
 int g_self_form = 1;
-bool use_w64(bool prescaled, bool short_keys, int mode) {
-  return prescaled && !short_keys && (g_self_form == 2 || (g_self_form == 1 && mode != 2));
+// query rows per workgroup of the wide kernel for this launch, or 0: attn_fwd_m16 (256)
+int wide_rows(bool prescaled, int fp8, bool gated, int Lk, int mode) {
+  if (g_self_form == 0 || !prescaled || fp8 != 0 || gated || Lk <= 4096 || mode == 2) return 0;
+  const int rows = g_self_form == 1 ? wq_default_rows(Lk) : g_self_form;
+  return wq_kernel(rows, mode, false) ? rows : 0;
 }
-#else
-constexpr bool use_w64(bool, bool, int) { return false; }
-#endif
 
 // the persistent form runs unsplit cross-attention launches in the zero-shift and online modes with >= 2 key tiles
 bool use_xattn_persistent(bool short_keys, int n_split, int mode, int64_t ntiles) {
@@ -1398,14 +1421,12 @@ bool use_xattn_persistent(bool short_keys, int n_split, int mode, int64_t ntiles
 
 }  // namespace
 
-#ifdef CP25_LAB_W64
-extern "C" int cp25_attn_self_select(int form) {  // (lab build only, see g_self_form)
-  if (form < 0 || form > 2) return CP25_ERR_INVAL;
+extern "C" int cp25_attn_self_select(int form) {
+  if (form != 0 && form != 1 && !wq_kernel(form, 0, false)) return CP25_ERR_INVAL;  // (a width not built)
   const int prev = g_self_form;
   g_self_form = form;
   return prev;
 }
-#endif
 
 extern "C" int cp25_attn_cross_select(int form) {
   if (form != 0 && form != 1) return CP25_ERR_INVAL;
@@ -1467,11 +1488,18 @@ static int attn_launch(const void* q, const void* k, const void* v, void* o, int
       return CP25_ERR_INVAL;
   }
   // unsplit self-attention with a workspace (cp25_attn_tail_workspace_bytes): the last, partial round as a tail split
+  const bool xk = Lk <= 4096;  // short-key launches (text cross-attention) get their own symbol in profiles
+  const float sl2 = prescaled ? 1.f : softmax_scale * 1.4426950408889634f;
+  const int mode = m16_mode(q_norm_bound, k_norm_bound, sl2, prescaled, !xk);
+  const bool gated = prescaled && kslots && m16_gated(q_norm_bound, k_norm_bound, !xk);
+  // query rows per workgroup: attn_fwd_m16's 256, or the wide kernel's where the launch is routed to it
+  const int wq_rows = wide_rows(prescaled, fp8, gated, Lk, mode);
+  const int qblk = wq_rows ? wq_rows : kQBlk;
   TailSeg tail[kMaxTailSegs];
   int n_tail = 0;
   if (n_split == 1 && fp8 == 0 && !kslots && workspace && !((uintptr_t)workspace & 15)) {
     size_t need = 0;
-    n_tail = plan_tail(B, H, Lq, Lk, tail, &need, nullptr);
+    n_tail = plan_tail(B, H, Lq, Lk, qblk, tail, &need, nullptr);
     if (ws_bytes < need) n_tail = 0;
   }
   AttnArgs a;
@@ -1482,7 +1510,7 @@ static int attn_launch(const void* q, const void* k, const void* v, void* o, int
   a.v_sb = v_strides[0]; a.v_sl = v_strides[1]; a.v_sh = v_strides[2];
   a.o_sb = o_strides[0]; a.o_sl = o_strides[1]; a.o_sh = o_strides[2];
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
-  a.nqb = (int)cdiv(Lq, kQBlk);
+  a.nqb = (int)cdiv(Lq, qblk);
   a.nsplit = n_split;
   a.tps = (int)tps;
   a.ntk_v = (int)ntiles;
@@ -1492,7 +1520,7 @@ static int attn_launch(const void* q, const void* k, const void* v, void* o, int
   a.s_init = fp8 == 2 ? -std::max(0.f, 1.13f * q_norm_bound * k_norm_bound - 15.f) : 0.f;
   a.o_part = n_split > 1 ? (float*)workspace : nullptr;
   a.lse_part = n_split > 1 ? (float*)workspace + (size_t)n_split * rows * kD : nullptr;
-  a.scale_log2 = prescaled ? 1.f : softmax_scale * 1.4426950408889634f;
+  a.scale_log2 = sl2;
   a.kbound = q_norm_bound > 0.f ? k_norm_bound : 0.f;  // a missing q bound: online (the kernel measures |q_row|)
   a.kslots = kslots;
   a.n_kslots = n_kslots;
@@ -1509,18 +1537,16 @@ static int attn_launch(const void* q, const void* k, const void* v, void* o, int
 #endif
   const int64_t nwg = (int64_t)a.nqb * B * H * n_split;
   if (nwg > 0x7fffffff) return CP25_ERR_INVAL;
-  const bool xk = Lk <= 4096;  // short-key launches (text cross-attention) get their own symbol in profiles
   if (fp8 == 2) {
     hipLaunchKernelGGL((xk ? attn_fwd_f8<1, 3> : attn_fwd_f8<0, 3>), dim3((unsigned)nwg), dim3(kThreads), 0, stream, a);
   } else if (fp8qk) {
     hipLaunchKernelGGL((xk ? attn_fwd_f8<1, 1> : attn_fwd_f8<0, 1>), dim3((unsigned)nwg), dim3(kThreads), 0, stream, a);
   } else {
-    const int mode = m16_mode(q_norm_bound, k_norm_bound, a.scale_log2, prescaled, !xk);
     void (*kern)(AttnArgs) = nullptr;
     void (*kern_tail)(AttnArgs) = nullptr;  // the tail segments' symbol (plan_tail: self-attention shapes only)
     int64_t grid = nwg;
     int threads = kThreads;
-    if (prescaled && kslots && m16_gated(q_norm_bound, k_norm_bound, !xk)) {
+    if (gated) {
       // the gated pair: blocks whose data-tight bound allows it (<= kGateFixed) run the fixed-shift loop with the
       // measured key bound, the others the online max
       hipLaunchKernelGGL((xk ? attn_fwd_m16<1, true, 0, false, 1> : attn_fwd_m16<0, true, 0, false, 1>),
@@ -1535,14 +1561,11 @@ static int attn_launch(const void* q, const void* k, const void* v, void* o, int
     } else {
 #define M16(P, M) kern = xk ? attn_fwd_m16<1, P, M> : attn_fwd_m16<0, P, M>; \
                   kern_tail = attn_fwd_m16<0, P, M, false, 0, 1>
-#ifdef CP25_LAB_W64
-      if (use_w64(prescaled, xk, mode)) {
-        kern = w64_kernel(mode, false);
-        kern_tail = w64_kernel(mode, true);
-        threads = kW64Threads;
-      } else
-#endif
-      if (prescaled) {
+      if (wq_rows) {
+        kern = wq_kernel(wq_rows, mode, false);
+        kern_tail = wq_kernel(wq_rows, mode, true);
+        threads = kWqThreads;
+      } else if (prescaled) {
         if (mode == 2) { M16(true, 2); } else if (mode == 1) { M16(true, 1); } else { M16(true, 0); }
       } else {
         if (mode == 2) { M16(false, 2); } else { M16(false, 0); }
@@ -1557,14 +1580,14 @@ static int attn_launch(const void* q, const void* k, const void* v, void* o, int
     for (int i = grid < nwg ? 0 : n_tail; i < n_tail; ++i) {
       const TailSeg& g = tail[i];
       const int b = g.bh / H, h = g.bh % H;
-      const int64_t row0 = (int64_t)g.qb_lo * kQBlk;
+      const int64_t row0 = (int64_t)g.qb_lo * qblk;
       AttnArgs t = a;
       t.q = a.q + b * a.q_sb + h * a.q_sh + row0 * a.q_sl;
       t.k = a.k + b * a.k_sb + h * a.k_sh;
       t.v = a.v + b * a.v_sb + h * a.v_sh;
       t.o = a.o + b * a.o_sb + h * a.o_sh + row0 * a.o_sl;
       t.B = 1; t.H = 1;
-      t.Lq = (int)(std::min<int64_t>(Lq, row0 + (int64_t)g.nblk * kQBlk) - row0);
+      t.Lq = (int)(std::min<int64_t>(Lq, row0 + (int64_t)g.nblk * qblk) - row0);
       t.qn_row0 = (int)row0;  // the sub-problem's query row 0 is token row0 (RoPE tables)
       t.nqb = g.nblk;
       t.nsplit = g.s;
@@ -1614,15 +1637,19 @@ extern "C" size_t cp25_attn_workspace_bytes(int B, int H, int Lq, int n_split) {
 
 extern "C" size_t cp25_attn_tail_workspace_bytes(int B, int H, int Lq, int Lk) {
   if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return 0;
+  // the shape alone does not say which kernel the launch takes (that needs the bounds): enough for either
   TailSeg seg[kMaxTailSegs];
-  size_t need = 0;
-  return plan_tail(B, H, Lq, Lk, seg, &need, nullptr) > 0 ? need : 0;
+  size_t need = 0, best = 0;
+  const int wide = g_self_form == 0 ? 0 : (g_self_form == 1 ? wq_default_rows(Lk) : g_self_form);
+  for (int qblk : {kQBlk, Lk > 4096 ? wide : 0})
+    if (qblk > 0 && plan_tail(B, H, Lq, Lk, qblk, seg, &need, nullptr) > 0) best = std::max(best, need);
+  return best;
 }
 
 extern "C" int cp25_attn_plan(int B, int H, int Lq, int Lk, int D) {
   if (D != kD) return CP25_ERR_DTYPE;
   if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return CP25_ERR_INVAL;
-  return plan_split(B, H, Lq, Lk);
+  return plan_split(B, H, Lq, Lk, kQBlk);  // (from the shape alone: attn_fwd_m16's query blocks)
 }
 
 extern "C" int cp25_attn_fwd(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
@@ -1708,10 +1735,13 @@ extern "C" const char* cp25_attn_kernel(int Lk, float softmax_scale, float q_nor
                        : (prescaled ? "attn_fwd_m16<cross, prescaled, online max, persistent>"
                                     : "attn_fwd_m16<cross, online max, persistent>");
   }
-  if (fp8 == 0 && prescaled == 1 && use_w64(true, Lk <= 4096, m16_mode(q_norm_bound, k_norm_bound, 1.f, true))) {
-    static const char* w64[3] = {"attn_fwd_w64<self, prescaled, fixed shift>", "attn_fwd_w64<self, prescaled, zero shift>",
-                                 "attn_fwd_w64<self, prescaled, online max>"};
-    return w64[m16_mode(q_norm_bound, k_norm_bound, 1.f, true)];
+  if (Lk > 4096 && prescaled) {
+    const int mode = m16_mode(q_norm_bound, k_norm_bound, 1.f, true, true);
+    const int rows = wide_rows(true, fp8, false, Lk, mode);  // (a gated pair returned above)
+    static const char* wq[2][2] = {
+        {"attn_fwd_wq<self, prescaled, 320 rows, fixed shift>", "attn_fwd_wq<self, prescaled, 320 rows, zero shift>"},
+        {"attn_fwd_wq<self, prescaled, 384 rows, fixed shift>", "attn_fwd_wq<self, prescaled, 384 rows, zero shift>"}};
+    if (rows) return wq[rows == 384][mode];
   }
   static const char* names[2][2][3] = {
       {{"attn_fwd_m16<self, fixed shift>", "?", "attn_fwd_m16<self, online max>"},

@@ -1,0 +1,554 @@
+// attn_fwd_wq (round 13): the DiT's long-key self-attention with ONE wave per SIMD and 16 kNQ query rows per wave,
+// 64 kNQ per workgroup (kNQ = 5: 320 rows, kNQ = 6: 384), gfx950, bf16 in / out, head dim 128. Replaces the same
+// reference op as attn_fwd_m16 (attn_fwd.hip): cosmos_predict2/_src/predict2/networks/attention.py:90-181,
+// softmax(Q K^T / sqrt(D)) V, no mask, non-causal.
+//
+// Why: every workgroup streams the whole K and V of its (b, h) from the L2 into the LDS once, so the
+// staging traffic of a launch is (Lq / R) Lk 512 B per (b, h) for R query rows per workgroup, and that traffic's energy
+// is what sets the power-limited clock of the loop (profiles/r6/w64/SUMMARY.md). attn_fwd_m16 has R = 256; here R = 320
+// or 384, and every K / V fragment read from the LDS feeds kNQ MFMAs instead of two.
+//
+// Arithmetic: every output element is the same MFMA chains, in the same order, on the same operands as attn_fwd_m16
+// (v_mfma_f32_16x16x32_bf16: S^T = K Q^T over the d steps s = 0..3 with the row's shift as the initial C; O^T += V^T P^T
+// over the key steps in key order; row sums by MFMA on an all-ones V^T row over the bf16 P; the same v_exp_f32, bf16
+// pack, in-kernel q RMSNorm + RoPE + prescale, fixed-shift rule floor(min(b_row + kPDrop, 126 - b_row)), split partials
+// and lse), so the outputs are bit-identical (tests/test_attn_wide_gpu.py). Zero shift (kMode 1) and fixed shift
+// (kMode 0) only: the online max, the gated pair, the fp8 forms and the cross-attention stay on attn_fwd_m16.
+//
+// Registers (one wave per SIMD: 256 VGPRs + 256 AGPRs per lane). "a"-constrained asm operands, which the compiler keeps
+// in the accumulator file and never touches between the asm MFMAs: O^T[16 db + 4 g + i][16 qb + c] (oacc[db][qb], 32 kNQ),
+// the row sums (lacc[qb], 4 kNQ), the all-ones operand (4) and the Q fragments of the first kQA query blocks (16 each:
+// what is left of 256). The other Q blocks, the shifts (minit, 4 kNQ) and the pipeline's S / P live in arch VGPRs.
+//
+// The in-wave software pipeline runs on 32-key HALF stages (with 64-key stages S^T and P^T of two stages are 48 kNQ
+// registers, which does not fit): S^T of two half stages is 16 kNQ, P^T of two is 8 kNQ. Half stage u (keys 32 u ..
+// 32 u + 31 of the workgroup's key range) has, in its MFMA stream, the row sums of P(u - 1) (kNQ), P.V(u - 1) (8 V^T
+// fragments x kNQ) and Q K^T(u + 1) (2 key blocks x 4 d steps x kNQ), and in the issue gaps between them the softmax of
+// S(u) (per query block 8 v_exp_f32 and 4 bf16 packs: 12 kNQ instructions, placed by the compile-time gap plan below),
+// the operand reads two fragments ahead (a ring of three) and the LDS-DMA pieces.
+//
+// The LDS keeps attn_fwd_m16's image: 64-key K and V tiles in 288-B rows, two buffers each, and ONE workgroup barrier
+// per 64 keys. Iteration t is the two half stages u = 2 t + 1 (A) and 2 t + 2 (B): both read V(t) (key step 0, then 1)
+// and K(t + 1) (key blocks 0-1, then 2-3) and nothing else, so the ten DMA pieces of K(t + 2) and V(t + 1) go to the
+// two buffers the previous iteration read. Each wave drains its pieces (vmcnt(0)) before the closing barrier, which
+// publishes them. The DMA is the bounds-checked buffer form: rows past the last key read as zeros, so the ragged tile
+// and the virtual tile the last iteration prefetches need no path of their own; scores of keys >= Lk are set to -inf
+// before their softmax (P = 0 exactly), per half stage.
+//
+// Prologue: K(0), K(1), V(0) by DMA, then iteration t = -1 without its P.V and without stage A's softmax: Q K^T(0),
+// softmax S(0), Q K^T(1). The loop then runs t = 0 .. ntk - 1; the last iteration's Q K^T and stage-B softmax work on
+// a virtual tile whose results no one reads.
+#include "attn_common.h"
+
+namespace cp25attn {
+namespace {
+
+constexpr int kAheadWq = 2;             // operand fragments read ahead of their MFMAs
+constexpr int kRingWq = kAheadWq + 1;
+static_assert(kWqThreads == 4 * 64, "one wave per SIMD");
+
+// ---- the gap plan of one half stage: 17 kNQ MFMA slots. Slot m < kNQ: the row sum of query block m; then fragment
+// f = (m - kNQ) / kNQ (0-7: V^T block db = f of P.V; 8-15: K fragment j = f - 8, key block j & 1, d step j >> 1) x query
+// block (m - kNQ) % kNQ. A fragment's first MFMA is its "read gap": the reads of the fragment kAheadWq later follow
+// it, and (stage A) DMA piece d < 10 rides in the read gap of fragment d, its M0 set in the gap before. The softmax's
+// 12 kNQ instructions (per query block e0 e1 c0 e2 e3 c1 e4 e5 c2 e6 e7 c3) take the other gaps in slot order. One
+// v_exp fills a gap's issue slots (8 of the MFMA's 16 cycles).
+constexpr int wq_stage(int nq) { return 17 * nq; }
+constexpr int wq_frag(int nq, int m) { return m < nq ? -1 : (m - nq) / nq; }
+constexpr int wq_qb(int nq, int m) { return m < nq ? m : (m - nq) % nq; }
+constexpr bool wq_read_gap(int nq, int m) { return m >= nq && (m - nq) % nq == 0; }
+constexpr int wq_sm_op(int nq, int m) {  // the softmax instruction in the gap after stage slot m, or -1
+  if (wq_read_gap(nq, m)) return -1;
+  int idx = 0;
+  for (int x = 0; x < m; ++x) idx += !wq_read_gap(nq, x);
+  return idx < 12 * nq ? idx : -1;
+}
+constexpr int wq_sm_count(int nq) {
+  int n = 0;
+  for (int m = 0; m < wq_stage(nq); ++m) n += wq_sm_op(nq, m) >= 0;
+  return n;
+}
+static_assert(wq_sm_count(5) == 60 && wq_sm_count(6) == 72, "every softmax instruction has a gap");
+// DMA piece d (0-4: K(t + 2), 5-9: V(t + 1)) in the gap after iteration slot M (stage A), or -1; its M0 one gap earlier
+constexpr int wq_dma_at(int nq, int M) {
+  return M < wq_stage(nq) && wq_read_gap(nq, M) && wq_frag(nq, M) < 10 ? wq_frag(nq, M) : -1;
+}
+constexpr int wq_m0_at(int nq, int M) { return wq_dma_at(nq, M + 1); }
+
+// the bounds-checked buffer descriptor of one K or V tile (rows past the tile's last key read as zero)
+__device__ __forceinline__ u32x4 tile_rsrc(const char* base, int64_t sl, int rows) {
+  const uint64_t p = (uint64_t)base;
+  const unsigned n = rows > 0 ? (unsigned)((rows - 1) * sl * 2 + 2 * kD) : 0u;
+  return u32x4{(unsigned)p, (unsigned)(p >> 32) & 0xffffu, n, 0x00020000u};
+}
+
+#define WQ_MFMA "v_mfma_f32_16x16x32_bf16 "
+
+template <int kNQ, int kMode, int kTail = 0>
+__global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
+  static_assert(kMode == 0 || kMode == 1, "kMode: 0 fixed shift, 1 zero shift");
+  static_assert(kNQ >= 4 && kNQ <= 6, "query blocks per wave");
+  __shared__ __attribute__((aligned(16))) char smem[kLds16];
+  constexpr bool kInit = kMode != 1;  // the shift rides in the Q K^T chains' initial C
+  constexpr int KB1 = kKBuf16, VB0 = 2 * kKBuf16;
+  constexpr int kR = kRingWq;
+  constexpr int kRowsW = 16 * kNQ;    // query rows per wave
+  constexpr int kRowsG = 4 * kRowsW;  // per workgroup
+  constexpr int kNS = wq_stage(kNQ);
+  // Q blocks whose fragments fit the accumulator file beside O^T, the row sums and the ones operand
+  constexpr int kQA = (256 - 36 * kNQ - 4) / 16 < kNQ ? (256 - 36 * kNQ - 4) / 16 : kNQ;
+
+  const int tile = xcd_remap(blockIdx.x, gridDim.x);
+  const int qblk = tile % a.nqb;
+  const int bhs = tile / a.nqb;
+  const int split = bhs % a.nsplit, bh = bhs / a.nsplit;
+  const int b = bh / a.H, h = bh % a.H;
+  const int key0 = split * a.tps * kKBlk;
+  const int Lk = min(a.Lk - key0, a.tps * kKBlk);
+  const int ntk = (Lk + kKBlk - 1) / kKBlk;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c16 = lane & 15;
+  const int g = lane >> 4;
+  const int row_w = qblk * kRowsG + wave * kRowsW;  // the wave's first query row
+
+  const unsigned short* qp = a.q + b * a.q_sb + h * a.q_sh;
+  const char* const kbase = (const char*)(a.k + b * a.k_sb + h * a.k_sh + (int64_t)key0 * a.k_sl);
+  const char* const vbase = (const char*)(a.v + b * a.v_sb + h * a.v_sh + (int64_t)key0 * a.v_sl);
+
+  // ---- LDS-DMA: piece p = wave + 4 j of a tile (18 per tile: waves 0-1 move 5, waves 2-3 move 4) is tile bytes
+  // [1024 p, +1024) of the 64 x 288-B image, lane l the 16 B at 16 l of it: row bb / 288, column bb % 288 (columns
+  // >= 256 are the row padding and re-read the tile's first 16 B), attn_fwd_m16's dma_tile. Bounds-checked buffer loads:
+  // rows past the tile's last key (the ragged tile, the virtual tiles past Lk) read as zero.
+  int dk[5], dv[5];
+#pragma unroll
+  for (int j = 0; j < 5; ++j) {
+    const int bb = 1024 * (wave + 4 * j) + 16 * lane;
+    const int row = bb / kKStride16, cb = bb - row * kKStride16;
+    dk[j] = cb < 2 * kD ? row * (int)(a.k_sl * 2) + cb : 0;
+    dv[j] = cb < 2 * kD ? row * (int)(a.v_sl * 2) + cb : 0;
+  }
+  const unsigned lds_wave = (unsigned)(uintptr_t)(lds_char_ptr)smem + 1024u * (unsigned)wave;
+  auto k_rsrc = [&](int t) __attribute__((always_inline)) {
+    return tile_rsrc(kbase + (int64_t)t * kKBlk * a.k_sl * 2, a.k_sl, min(Lk - t * kKBlk, kKBlk));
+  };
+  auto v_rsrc = [&](int t) __attribute__((always_inline)) {
+    return tile_rsrc(vbase + (int64_t)t * kKBlk * a.v_sl * 2, a.v_sl, min(Lk - t * kKBlk, kKBlk));
+  };
+  // M0 = the wave's LDS destination of a piece (an SALU write; the load that reads it is at least one MFMA later)
+  auto set_m0 = [&](unsigned dst, auto OFFC) __attribute__((always_inline)) {
+    asm volatile("s_add_u32 m0, %0, %1" ::"s"(dst), "i"(decltype(OFFC)::value) : "memory");
+  };
+  auto dma_load = [&](const u32x4& rs, int off) __attribute__((always_inline)) {
+    asm volatile("buffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(off), "s"(rs) : "memory");
+  };
+  // one whole tile (prologue): pieces j = 0..4 into LDS byte dst + 4096 j (dst includes the wave's 1024 wave)
+  auto dma_tile = [&](const u32x4& rs, const int* offs, unsigned dst) __attribute__((always_inline)) {
+    static_for<5>([&](auto JC) __attribute__((always_inline)) {
+      constexpr int j = decltype(JC)::value;
+      if (j < 4 || wave < 2) {
+        set_m0(dst, std::integral_constant<int, 4096 * j>{});
+        asm volatile("s_nop 0" ::: "memory");
+        dma_load(rs, offs[j]);
+      }
+    });
+  };
+
+  // K(0), K(1), V(0) first: their flight overlaps the Q loads and the q normalisation
+  dma_tile(k_rsrc(0), dk, lds_wave);
+  dma_tile(k_rsrc(1), dk, lds_wave + KB1);
+  dma_tile(v_rsrc(0), dv, lds_wave + VB0);
+
+  // ---- Q fragments Q[16 qb + c][32 s + 8 g .. +7] of rows row_w + 16 qb + c ----
+  bf16x8 qa[kNQ][4];
+#pragma unroll
+  for (int qb = 0; qb < kNQ; ++qb) {
+    const int r = row_w + 16 * qb + c16;
+    const unsigned short* src = qp + (int64_t)min(r, a.Lq - 1) * a.q_sl + 8 * g;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) qa[qb][s] = *reinterpret_cast<const bf16x8*>(src + 32 * s);
+  }
+  if (a.qn_w != nullptr) {
+    // attn_fwd_m16's in-kernel q RMSNorm + RoPE + prescale, operation for operation, on the kNQ query blocks
+    bf16x8 wv[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) wv[s] = *reinterpret_cast<const bf16x8*>(a.qn_w + 32 * s + 8 * g);
+    const bool rope = a.qn_cos != nullptr;
+    const f32x2 scale2 = {a.qn_scale, a.qn_scale};
+#pragma unroll
+    for (int qb = 0; qb < kNQ; ++qb) {
+      const int r = row_w + 16 * qb + c16;
+      f32x4 rc[2][2], rsn[2][2];
+      if (rope) {
+        const int64_t t0 = (a.qn_row0 + min(r, a.Lq - 1)) * 64 + 8 * g;
+#pragma unroll
+        for (int s1 = 0; s1 < 2; ++s1)
+#pragma unroll
+          for (int hf = 0; hf < 2; ++hf) {
+            rc[s1][hf] = *reinterpret_cast<const f32x4*>(a.qn_cos + t0 + 32 * s1 + 4 * hf);
+            rsn[s1][hf] = *reinterpret_cast<const f32x4*>(a.qn_sin + t0 + 32 * s1 + 4 * hf);
+          }
+      }
+      f32x2 x[4][4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          x[s][q] = f32x2{static_cast<float>(qa[qb][s][2 * q]), static_cast<float>(qa[qb][s][2 * q + 1])};
+      f32x2 c01[8], c23[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        c01[e] = f32x2{x[0][e >> 1][e & 1], x[1][e >> 1][e & 1]};
+        c23[e] = f32x2{x[2][e >> 1][e & 1], x[3][e >> 1][e & 1]};
+      }
+      const f32x2 p01 = hn2_sumsq8(c01), p23 = hn2_sumsq8(c23);
+      const f32x2 aa = p01 + p23;
+      float ss = aa.x + aa.y;
+      ss += __shfl_xor(ss, 32);
+      ss += __shfl_xor(ss, 16);
+      const float rstd = hn_rstd(ss, a.qn_eps);
+      const f32x2 rstd2 = {rstd, rstd};
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          x[s][q] = hn2_norm(x[s][q], rstd2,
+                             f32x2{static_cast<float>(wv[s][2 * q]), static_cast<float>(wv[s][2 * q + 1])});
+      f32x2 y[4][4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) y[s][q] = x[s][q];
+      if (rope) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const f32x4 cc = rc[s & 1][q >> 1], sn = rsn[s & 1][q >> 1];
+            const int o = 2 * (q & 1);
+            y[s][q] = hn2_rope(x[s][q], x[s ^ 2][q], s < 2 ? -1.f : 1.f, f32x2{cc[o], cc[o + 1]},
+                               f32x2{sn[o], sn[o + 1]});
+          }
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const bf16x2v hh = __builtin_convertvector(y[s][q] * scale2, bf16x2v);
+          qa[qb][s][2 * q] = hh.x;
+          qa[qb][s][2 * q + 1] = hh.y;
+        }
+    }
+  }
+
+  // ---- the rows' softmax shifts (fixed: from |q_row| and the key bound, attn_fwd_m16's rule) ----
+  float m_run[kNQ];
+#pragma unroll
+  for (int qb = 0; qb < kNQ; ++qb) m_run[qb] = 0.f;
+  if constexpr (kMode == 0) {
+#pragma unroll
+    for (int qb = 0; qb < kNQ; ++qb) {
+      float qq = 0.f;
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float x = static_cast<float>(qa[qb][s][e]);
+          qq = fmaf(x, x, qq);
+        }
+      const float b_row = sqrtf(group4_sum(qq)) * a.kbound;
+      m_run[qb] = floorf(fminf(b_row + kPDrop, 126.f - b_row));
+    }
+  }
+  f32x4 minit[kNQ];
+#pragma unroll
+  for (int qb = 0; qb < kNQ; ++qb) {
+    minit[qb] = f32x4{-m_run[qb], -m_run[qb], -m_run[qb], -m_run[qb]};
+    // opaque from here on: a broadcast the compiler may otherwise rematerialise right ahead of the asm MFMA that takes
+    // it as C (a VALU write -> MFMA operand hazard it does not pad for asm)
+    asm volatile("" : "+v"(minit[qb]));
+  }
+
+  // O^T, the row sums, the ones operand and the first kQA Q blocks into the accumulator file (v_accvgpr_write -> MFMA
+  // operand: 2 wait states, inside the statement that ties each there); the other Q blocks opaque in VGPRs
+  f32x4 oacc[8][kNQ], lacc[kNQ];
+#pragma unroll
+  for (int db = 0; db < 8; ++db)
+#pragma unroll
+    for (int qb = 0; qb < kNQ; ++qb) {
+      oacc[db][qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+      asm volatile("s_nop 2" : "+a"(oacc[db][qb]));
+    }
+#pragma unroll
+  for (int qb = 0; qb < kNQ; ++qb) {
+    lacc[qb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    asm volatile("s_nop 2" : "+a"(lacc[qb]));
+  }
+  static_for<kNQ>([&](auto QC) __attribute__((always_inline)) {
+    constexpr int qb = decltype(QC)::value;
+    (void)qa;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if constexpr (qb < kQA) asm volatile("s_nop 2" : "+a"(qa[qb][s]));
+      else asm volatile("s_nop 2" : "+v"(qa[qb][s]));
+    }
+  });
+  // the all-ones A operand of the row-sum MFMAs, in the accumulator file (as a VGPR constant the compiler may
+  // rematerialise it with a v_mov right ahead of the first row-sum MFMA)
+  typedef short s16x8v __attribute__((ext_vector_type(8)));
+  bf16x8 ones8 = __builtin_bit_cast(bf16x8, s16x8v{0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80});
+  asm volatile("s_nop 2" : "+a"(ones8));
+  const unsigned k_rd_lds = (unsigned)(uintptr_t)(lds_char_ptr)(smem + c16 * kKStride16 + 16 * g);
+  const unsigned v_rd_lds =
+      (unsigned)(uintptr_t)(lds_char_ptr)(smem + VB0 + (4 * g + (c16 >> 2)) * kVStride16 + 8 * (c16 & 3));
+
+  f32x4 S[2][2][kNQ];  // S^T of two half stages: [half-stage parity][key block of the half][query block]
+  bf16x8 P[2][kNQ];    // P^T of two half stages: [half-stage parity][query block]
+  bf16x8 ring[kR];
+  float ex[2];
+  unsigned pk[4];
+  unsigned k_cur = 0, v_cur = 0;  // this iteration's K(t + 1) / V(t) read bases
+
+  // fragment F of an iteration (stage F / 16, f = F % 16): f < 8 the V^T fragment (db = f, key step = stage: two
+  // transposed reads), f >= 8 the K fragment (key block 2 stage + ((f - 8) & 1), d step (f - 8) >> 1)
+  auto issue = [&](auto FC, auto SLOTC) __attribute__((always_inline)) {
+    constexpr int F = decltype(FC)::value, slot = decltype(SLOTC)::value;
+    constexpr int st = F / 16, f = F % 16;
+    (void)ring;
+    (void)k_cur;
+    (void)v_cur;
+    if constexpr (f >= 8) {
+      constexpr int j = f - 8;
+      constexpr int off = (2 * st + (j & 1)) * 16 * kKStride16 + 64 * (j >> 1);
+      asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[slot]) : "v"(k_cur), "i"(off));
+    } else {
+      constexpr int off = 32 * st * kVStride16 + 32 * f;
+      s16x4 lo, hi;
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(v_cur), "i"(off));
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(v_cur), "i"(off + 16 * kVStride16));
+      typedef short s16x8 __attribute__((ext_vector_type(8)));
+      const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+      ring[slot] = __builtin_bit_cast(bf16x8, r);
+    }
+  };
+
+  // scores of keys >= Lk of the half stage whose first key is k0 (S[SP]): -inf, so P = 0 exactly. Rare (the ragged
+  // tile and the virtual one); the nops let the MFMAs that wrote S[SP] finish
+  auto mask_keys = [&](auto SPC, int k0) __attribute__((always_inline)) {
+    constexpr int SP = decltype(SPC)::value;
+    if (__builtin_expect(k0 + 32 > Lk, 0)) {
+      asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
+#pragma unroll
+      for (int kbl = 0; kbl < 2; ++kbl)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (k0 + 16 * kbl + 4 * g + i >= Lk) {
+#pragma unroll
+            for (int qb = 0; qb < kNQ; ++qb) S[SP][kbl][qb][i] = -INFINITY;
+          }
+    }
+  };
+
+  // One iteration t: stage A (u = 2 t + 1) then stage B (u = 2 t + 2). Stage ST's row sums and P.V read P[ST] and
+  // V(t)'s key step ST; its Q K^T reads K(t + 1)'s key blocks 2 ST, 2 ST + 1 and writes S[ST]; its softmax reads
+  // S[1 - ST] and writes P[1 - ST]. FULL: the loop's iteration; else the prologue (t = -1: no P.V, no stage-A softmax,
+  // no DMA).
+  auto body = [&](auto FULLC, int t) __attribute__((always_inline)) {
+    constexpr bool FULL = decltype(FULLC)::value;
+    constexpr int NF = FULL ? 32 : 16;  // live fragments, in order
+    constexpr auto frag_of = [](int n) constexpr { return FULL ? n : (n < 8 ? 8 + n : 16 + n); };
+    constexpr auto seq_of = [](int F) constexpr { return FULL ? F : (F < 16 ? F - 8 : F - 16); };
+    constexpr auto nreads = [](int F) constexpr { return F % 16 < 8 ? 2 : 1; };
+    k_cur = k_rd_lds + (((t + 1) & 1) ? (unsigned)KB1 : 0u);
+    v_cur = v_rd_lds + ((t & 1) ? (unsigned)kVBuf16 : 0u);
+    u32x4 rk = {0u, 0u, 0u, 0u}, rv = {0u, 0u, 0u, 0u};
+    unsigned dst_k = 0, dst_v = 0;
+    if constexpr (FULL) {
+      mask_keys(std::integral_constant<int, 1>{}, 64 * t + 32);
+      rk = k_rsrc(t + 2);  // past the last tile: an empty range, the pieces land as zeros
+      rv = v_rsrc(t + 1);
+      dst_k = lds_wave + ((t & 1) ? (unsigned)KB1 : 0u);
+      dst_v = lds_wave + (unsigned)VB0 + (((t + 1) & 1) ? (unsigned)kVBuf16 : 0u);
+    }
+    static_for<kAheadWq>([&](auto IC) __attribute__((always_inline)) {
+      constexpr int n = decltype(IC)::value;
+      issue(std::integral_constant<int, frag_of(n)>{}, std::integral_constant<int, n % kR>{});
+    });
+    __builtin_amdgcn_sched_barrier(0);
+    static_for<2 * kNS>([&](auto MC) __attribute__((always_inline)) {
+      constexpr int M = decltype(MC)::value;
+      constexpr int st = M / kNS, m = M % kNS;
+      constexpr int f = wq_frag(kNQ, m), qb = wq_qb(kNQ, m);
+      constexpr int F = 16 * st + (f < 0 ? 0 : f);
+      constexpr bool has_mfma = f >= 8 || FULL;
+      constexpr bool has_sm = st == 1 || FULL;
+      (void)S;  // (asm operands, named: clang's implicit capture into a generic lambda misses them otherwise)
+      (void)ex;
+      (void)pk;
+      (void)oacc;
+      (void)lacc;
+      (void)ones8;
+      (void)P;
+      (void)minit;
+      (void)qa;
+      (void)ring;
+      (void)rk;
+      (void)rv;
+      (void)dst_k;
+      (void)dst_v;
+      if constexpr (m == 0 && st == 1) {
+        if constexpr (!FULL) asm volatile("s_nop 15" ::: "memory");  // no MFMA ahead of the softmax's first S reads
+        mask_keys(std::integral_constant<int, 0>{}, 64 * (t + 1));
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (has_mfma) {
+        if constexpr (f >= 0 && qb == 0) {  // fragment F opens: its reads (not the later fragments') have landed
+          constexpr int n = seq_of(F);
+          constexpr int pending = [=]() constexpr {
+            int p = 0;
+            for (int i = 1; i < kAheadWq; ++i)
+              if (n + i < NF) p += nreads(frag_of(n + i));
+            return p;
+          }();
+          asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(pending), "v"(ring[n % kR]) : "memory");
+        }
+        if constexpr (f < 0) {  // row sums: all-ones x P^T
+          asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+a"(lacc[qb]) : "a"(ones8), "v"(P[st][qb]));
+        } else if constexpr (f < 8) {  // O^T[db] += V^T(db, key step st) P^T
+          asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+a"(oacc[f][qb]) : "v"(ring[seq_of(F) % kR]), "v"(P[st][qb]));
+        } else {  // S^T[kbl] (+)= K(kbl, s) Q^T(s)
+          constexpr int kbl = (f - 8) & 1, s = (f - 8) >> 1;
+          constexpr int ri = seq_of(F) % kR;
+          if constexpr (qb < kQA) {
+            if constexpr (s == 0 && kInit)
+              asm volatile(WQ_MFMA "%0, %1, %2, %3"
+                           : "=&v"(S[st][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]), "v"(minit[qb]));
+            else if constexpr (s == 0)
+              asm volatile(WQ_MFMA "%0, %1, %2, 0" : "=&v"(S[st][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]));
+            else
+              asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+v"(S[st][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]));
+          } else {
+            if constexpr (s == 0 && kInit)
+              asm volatile(WQ_MFMA "%0, %1, %2, %3"
+                           : "=&v"(S[st][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]), "v"(minit[qb]));
+            else if constexpr (s == 0)
+              asm volatile(WQ_MFMA "%0, %1, %2, 0" : "=&v"(S[st][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]));
+            else
+              asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+v"(S[st][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]));
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      // ---- the gap after slot M ----
+      if constexpr (has_mfma && f >= 0 && qb == 0) {
+        constexpr int n = seq_of(F) + kAheadWq;
+        if constexpr (n < NF) issue(std::integral_constant<int, frag_of(n)>{}, std::integral_constant<int, n % kR>{});
+      }
+      if constexpr (FULL) {
+        constexpr int dm = wq_m0_at(kNQ, M), dl = wq_dma_at(kNQ, M);
+        if constexpr (dm >= 0) {  // M0 of piece dm (j = dm % 5 of K(t + 2), then of V(t + 1))
+          constexpr int j = dm % 5;
+          if (j < 4 || wave < 2) set_m0(dm < 5 ? dst_k : dst_v, std::integral_constant<int, 4096 * j>{});
+        }
+        if constexpr (dl >= 0) {
+          constexpr int j = dl % 5;
+          if (j < 4 || wave < 2) dma_load(dl < 5 ? rk : rv, dl < 5 ? dk[j] : dv[j]);
+        }
+      }
+      if constexpr (has_sm) {
+        if constexpr (!has_mfma) asm volatile("s_nop 1" ::: "memory");  // trans -> VALU use without an MFMA between
+        constexpr int op = wq_sm_op(kNQ, m);
+        if constexpr (op >= 0) {
+          constexpr int q = op / 12, r = op % 12, pair = r / 3, w = r % 3;
+          if constexpr (w < 2) {
+            constexpr int j = 2 * pair + w;
+            asm volatile("v_exp_f32 %0, %1" : "=v"(ex[w]) : "v"(S[1 - st][j >> 2][q][j & 3]));
+          } else {
+            // the bf16 pack as a compiler conversion (v_cvt_pk_bf16_f32), pinned to this gap by the asm statement that
+            // uses it
+            pk[pair] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ex[0], ex[1]}, bf16x2v));
+            asm volatile("" ::"v"(pk[pair]));
+            if constexpr (pair == 3) P[1 - st][q] = __builtin_bit_cast(bf16x8, u32x4{pk[0], pk[1], pk[2], pk[3]});
+          }
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    if constexpr (FULL) {
+      // P stays allocated to the end of the iteration: no register an MFMA of this iteration reads is handed to a
+      // load of the same iteration (an asm load may land before the MFMA issued just ahead of it read its operand)
+      static_for<kNQ>([&](auto QC) __attribute__((always_inline)) {
+        constexpr int qb = decltype(QC)::value;
+        (void)P;
+        asm volatile("" ::"v"(P[0][qb]), "v"(P[1][qb]));
+      });
+    }
+    // this wave's DMA pieces landed. Every piece is drained here: leaving pieces in flight across the barrier
+    // (vmcnt(N) > 0) gave wrong results in every variant tried on gfx950; they are issued in the
+    // first third of the iteration instead, so the drain finds them landed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // K(0), K(1), V(0)
+  __builtin_amdgcn_s_barrier();
+  body(std::false_type{}, -1);
+  for (int t = 0; t < ntk; ++t) body(std::true_type{}, t);
+
+  // ---- epilogue: O^T[16 db + 4 g + i][16 qb + c] = oacc[db][qb][i]: row row_w + 16 qb + c ----
+  asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last MFMAs' accumulator writes -> v_accvgpr_read
+#pragma unroll
+  for (int db = 0; db < 8; ++db)
+#pragma unroll
+    for (int qb = 0; qb < kNQ; ++qb) asm volatile("s_nop 0" : "+a"(oacc[db][qb]));
+#pragma unroll
+  for (int qb = 0; qb < kNQ; ++qb) asm volatile("s_nop 0" : "+a"(lacc[qb]));
+#pragma unroll
+  for (int qb = 0; qb < kNQ; ++qb) {
+    const int q_row = row_w + 16 * qb + c16;
+    const float l_tot = lacc[qb][0];
+    float inv = 1.f / l_tot;
+    // contract guard: a norm bound below the real norms can only show as an overflowed row sum
+    if (l_tot > 3.0e38f) inv = __uint_as_float(0x7fc00000u);
+    if (q_row >= a.Lq) continue;
+    if (a.nsplit > 1) {
+      const int64_t row = ((int64_t)(split * a.B + b) * a.H + h) * a.Lq + q_row;
+      float* op = a.o_part + row * kD + 4 * g;
+#pragma unroll
+      for (int db = 0; db < 8; ++db) {
+        f32x4 w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[e] = oacc[db][qb][e] * inv;
+        *reinterpret_cast<f32x4*>(op + 16 * db) = w;
+      }
+      if (g == 0) a.lse_part[row] = m_run[qb] + __log2f(l_tot);
+    } else {
+      unsigned short* op = a.o + b * a.o_sb + h * a.o_sh + (int64_t)q_row * a.o_sl + 4 * g;
+#pragma unroll
+      for (int db = 0; db < 8; ++db) {
+        u16x4 w;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) w[e] = f2bf(oacc[db][qb][e] * inv);
+        *reinterpret_cast<u16x4*>(op + 16 * db) = w;
+      }
+    }
+  }
+}
+
+#undef WQ_MFMA
+
+}  // namespace
+
+// Built: 320 and 384 rows, fixed shift. Every long-key launch with usable norm bounds is in the fixed mode (m16_mode's
+// whole_ok, round 6), so the zero-shift form (kMode 1: the same stream without the initial C) has no launch to serve
+// and is not instantiated.
+AttnKernel wq_kernel(int rows, int mode, bool tail) {
+  if (mode != 0) return nullptr;
+  if (rows == 320) return tail ? attn_fwd_wq<5, 0, 1> : attn_fwd_wq<5, 0>;
+  if (rows == 384) return tail ? attn_fwd_wq<6, 0, 1> : attn_fwd_wq<6, 0>;
+  return nullptr;
+}
+
+}  // namespace cp25attn

@@ -211,6 +211,19 @@ int cp25_attn_plan(int B, int H, int Lq, int Lk, int D);
  * form, or CP25_ERR_INVAL for another value. */
 int cp25_attn_cross_select(int form);
 
+/* Kernel form of the long-key self-attention launches (Lk > 4096) of cp25_attn_fwd_prescaled / _kslots / _qnorm that
+ * are bf16, not a gated pair and whose norm bounds give the fixed-shift mode (every long-key launch with a bound
+ * product <= 110): 1 (default) the library's routing, attn_fwd_wq (one wave per SIMD) with 384 query rows per
+ * workgroup past 8192 keys and 320 up to there (a third / a fifth less K / V staging traffic per launch than
+ * attn_fwd_m16's 256-row blocks); 0 attn_fwd_m16 everywhere; 320 / 384 that width
+ * wherever attn_fwd_wq supports the launch (a width this library was not built with is refused). Every form computes
+ * each output row with the same operations in the same order, so whole launches are bit-identical; the forms differ
+ * in which rows a planned launch's tail round computes as merged key splits (cp25_attn_tail_workspace_bytes covers
+ * the selected form). Online-max, gated, fp8 and short-key launches always run attn_fwd_m16 / attn_fwd_f8.
+ * cp25_attn_kernel names the kernel a launch takes under the current form. Set only through this call, never from
+ * the environment. Returns the previous form, or CP25_ERR_INVAL for another value. */
+int cp25_attn_self_select(int form);
+
 /* 3D neighborhood attention: every query of the (T, Hg, Wg) token grid (token = (t Hg + h) Wg + w, L = T Hg Wg)
  * attends the box of window[0] x window[1] x window[2] keys (dilation[i] apart along axis i) that the host plan
  * assigns to its tile; softmax over those keys only, bf16 in / out, fp32 accumulation, P rounded to bf16 before P V.

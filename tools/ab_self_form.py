@@ -1,9 +1,11 @@
-"""A/B of the self-attention kernel forms inside the metric's sampler evaluation (round 6): attn_fwd_m16 vs attn_fwd_w64
-(cp25_attn_self_select 0 / 2), evaluation by evaluation in one process, in ABBA order so that clock drift over the run
-cancels. The bench.py workload (Predict2.5-2B Image2World 704x1280x121f, CFG 2, B = 2, L = 109 120).
+"""A/B of the self-attention kernel forms inside the metric's sampler evaluation: attn_fwd_m16 (cp25_attn_self_select
+0) against attn_fwd_wq at a forced width (320, or 384 where built), evaluation by evaluation in one process, in ABBA
+order so that clock drift over the run cancels. The bench.py workload (Predict2.5-2B Image2World 704x1280x121f, CFG 2,
+B = 2, L = 109 120).
 
-  python tools/ab_self_form.py [--pairs 6] [--norm-weights lo,hi]
-Prints one JSON line: ms per evaluation for each form (list and median) and their ratio.
+  python tools/ab_self_form.py [--pairs 6] [--forms 320[,384]] [--norm-weights lo,hi]
+Prints one JSON line: ms per evaluation for each form (list and median), each width's ratio to form 0 and form 0's own
+spread (max - min) / median, the run's resolution.
 """
 import argparse
 import json
@@ -20,6 +22,7 @@ import torch  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=6)
+    ap.add_argument("--forms", default="320", help="comma-separated widths to set against form 0")
     ap.add_argument("--norm-weights", default="", help="lo,hi: q/k norm weights uniform in [lo, hi] (online max)")
     a = ap.parse_args()
     from cosmos_predict2 import _native as N
@@ -61,18 +64,25 @@ def main():
             torch.cuda.synchronize()
             return ev0.elapsed_time(ev1)
 
-        for f in (0, 2, 0, 2):  # warm both
+        widths = [int(x) for x in a.forms.split(",")]
+        for f in [0] + widths + [0] + widths:  # warm all
             one(f)
-        t = {0: [], 2: []}
-        for i in range(a.pairs):
-            order = (0, 2) if i % 2 == 0 else (2, 0)
-            for f in order:
-                t[f].append(round(one(f), 2))
+        t = {f: [] for f in [0] + widths}
+        kernels = {}
+        for wd in widths:
+            for i in range(a.pairs):
+                order = (0, wd) if i % 2 == 0 else (wd, 0)
+                for f in order:
+                    t[f].append(round(one(f), 2))
+            N.attn_self_select(wd)
+            kernels[wd] = model.net.attention_kernels(state_t * (h // 16) * (w // 16))["self"]
         N.attn_self_select(1)
     med = {f: float(np.median(v)) for f, v in t.items()}
-    print(json.dumps({"m16_ms_per_eval": t[0], "w64_ms_per_eval": t[2], "m16_median": med[0], "w64_median": med[2],
-                      "w64_over_m16": med[2] / med[0], "norm_weights": a.norm_weights or "ones (init)",
-                      "kernels": model.net.attention_kernels(state_t * (h // 16) * (w // 16))}))
+    print(json.dumps({"ms_per_eval": {str(f): v for f, v in t.items()}, "median": {str(f): m for f, m in med.items()},
+                      "over_form0": {str(f): med[f] / med[0] for f in widths},
+                      "form0_spread": (max(t[0]) - min(t[0])) / med[0],
+                      "norm_weights": a.norm_weights or "ones (init)", "kernels_forced": {str(f): k for f, k in kernels.items()},
+                      "kernels_default": model.net.attention_kernels(state_t * (h // 16) * (w // 16))}))
 
 
 if __name__ == "__main__":

@@ -98,10 +98,13 @@ def main():
                          "+ RoPE + prescale itself (cp25_attn_fwd_prescaled_qnorm, the DiT's default since round 4)")
     ap.add_argument("--lib", default="", help="lab build of libcp25.so to load instead of the in-tree one")
     ap.add_argument("--self-form", type=int, default=-1,
-                    help="w64 lab library (tools/lab/w64/build_lab.sh, with --lib): prescaled self-attention form, 0 attn_fwd_m16, 1 w64 in the zero / fixed modes, 2 w64 in all (cp25_attn_self_select)")
+                    help="long-key prescaled self-attention form (cp25_attn_self_select): 0 attn_fwd_m16 everywhere, "
+                         "1 the library's routing, 320 / 384 that width of attn_fwd_wq")
     ap.add_argument("--ab", type=int, default=0,
-                    help="A/B: after the timing, N more rounds alternating attn_fwd_m16 / attn_fwd_w64 launches "
-                         "(iters each), reported as ms lists per form")
+                    help="A/B: after the timing, N more rounds alternating the self-attention forms 0 (attn_fwd_m16), "
+                         "320 and 384 (attn_fwd_wq; the widths this library is built with), iters launches each, "
+                         "reported as ms lists per form, with each form's kernel name and whether its output is "
+                         "bit-identical to form 0's")
     ap.add_argument("--ab-libs", default="",
                     help="comma-separated lab builds of libcp25.so: after the timing, --ab rounds alternating the "
                          "loaded library and these (rotating order, iters launches each), reported as ms lists per "
@@ -192,19 +195,39 @@ def main():
     flop = 4.0 * a.B * a.H * a.L * Lk * 128
     ab = None
     if a.ab > 0 and not a.ab_libs:
-        ab = {"m16": [], "w64": []}
         prev = N.attn_self_select(0)
-        for _ in range(a.ab):
-            for form, key in ((0, "m16"), (1, "w64")):
+        forms = [0]
+        for f in (320, 384):  # the widths this library is built with
+            try:
+                N.attn_self_select(f)
+                forms.append(f)
+            except ValueError:  # CP25_ERR_INVAL: not built
+                pass
+        ms_f, names, same, o0 = {f: [] for f in forms}, {}, {}, None
+        for r in range(a.ab):
+            for form in forms[r % len(forms):] + forms[:r % len(forms)]:
                 N.attn_self_select(form)
                 N.attn_fwd(q, k, v, out=o, n_split=ns, norm_bounds=nb, **pre)
+                torch.cuda.synchronize()
+                if r == 0:
+                    names[form] = N.attn_kernel_name(Lk, norm_bounds=nb, prescaled=a.prescaled)
+                    if form == 0:
+                        o0 = o.clone()
                 e0.record(st)
                 for _ in range(a.iters):
                     N.attn_fwd(q, k, v, out=o, n_split=ns, norm_bounds=nb, **pre)
                 e1.record(st)
                 torch.cuda.synchronize()
-                ab[key].append(round(e0.elapsed_time(e1) / a.iters, 3))
+                ms_f[form].append(round(e0.elapsed_time(e1) / a.iters, 3))
+        for form in forms:  # (after the timing: form 0's output is known by then whatever the rotation)
+            N.attn_self_select(form)
+            N.attn_fwd(q, k, v, out=o, n_split=ns, norm_bounds=nb, **pre)
+            torch.cuda.synchronize()
+            same[form] = {"equal": bool(torch.equal(o, o0)),
+                          "rel_l2": float((o.float() - o0.float()).norm() / o0.float().norm())}
         N.attn_self_select(prev)
+        ab = {"ms": ms_f, "median": {f: sorted(v_)[len(v_) // 2] for f, v_ in ms_f.items()}, "kernels": names,
+              "vs_form0": same}
     if a.ab_libs:
         libs = {os.path.basename(a.lib) or "libcp25.so": N.load_library()}
         for path in a.ab_libs.split(","):

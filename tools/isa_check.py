@@ -27,7 +27,7 @@ def compile_asm(src, out=None, extra=()):
 
 
 def _compile_asm(src, out, extra=()):
-    unit_flags = ["-fno-honor-nans", "-fno-slp-vectorize"] if os.path.basename(src).startswith(("attn_fwd", "vae_attn")) \
+    unit_flags = ["-fno-honor-nans", "-fno-slp-vectorize"] if os.path.basename(src).startswith(("attn_fwd", "attn_wide", "vae_attn")) \
         else []  # the Makefile's per-unit flags
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
            "-fhip-fp32-correctly-rounded-divide-sqrt", "-I" + os.path.join(ROOT, "include"),

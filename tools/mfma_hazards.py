@@ -1,4 +1,4 @@
-"""Static check of asm-MFMA operand hazards the compiler does not pad (round 6, attn_fwd_w64): a VALU instruction
+"""Static check of asm-MFMA operand hazards the compiler does not pad (the attention kernels whose MFMAs are inline asm: attn_fwd_wq): a VALU instruction
 (v_mov, v_accvgpr_write, v_cvt, ...) writing a register that an MFMA within the next `need` wait states reads as
 A / B / C. Wait states: s_nop N counts N + 1, any other instruction 1. Usage: mfma_hazards.py file.s [kernel-substring]
 Prints the hazards; exit status 1 if any."""
