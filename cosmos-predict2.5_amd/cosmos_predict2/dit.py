@@ -437,7 +437,7 @@ class MinimalV1LVGDiT:
         if not (self.data_tight_k_bound and attn_kw.get("prescaled") and self.attention_precision == "bf16"):
             return None
         qb, kb = attn_kw["norm_bounds"]
-        if qb * kb <= 110.0:  # the weight bounds already give the fixed shift (attn_fwd.hip m16_mode, kGateFixed)
+        if qb * kb <= 110.0:  # the weight bounds already give the fixed shift (attn_route.h attn_route, kGateFixed)
             return None
         return torch.zeros((64, 32), dtype=torch.float32, device=self.device)
 

@@ -2,33 +2,17 @@
 // attn_wide.hip: attn_fwd_wq): the argument block, the tile geometry and the small device helpers.
 #pragma once
 #include "cp25_common.h"
+#include "attn_route.h"
 
 #include <algorithm>
 #include <type_traits>
 
 namespace cp25attn {
 
-constexpr int kD = 128;        // head dim
 constexpr int kWaves = 8;      // waves per workgroup
 constexpr int kQRows = 32;     // query rows per wave
-constexpr int kQBlk = kWaves * kQRows;  // 256 query rows per workgroup
-constexpr int kKBlk = 64;      // keys per tile
-constexpr int kThreads = kWaves * 64;
-// Softmax-shift ranges (log2 units). A term is 2^(s - shift) <= 2^kTop, so a row sum is <= Lk 2^96 and O = sum P v is
-// <= Lk 2^96 max|v|: inside fp32 (2^128) while max|v| Lk < 2^32, e.g. |v| < 2.6e4 at config 4's Lk = 163 800 (the
-// DiT's v is a bf16 projection of a normalised row, orders of magnitude smaller; checked at the top of the window
-// over 163 840 keys with |v| ~ 400 by tests/test_attn_m16_gpu.py::test_m16_zero_shift_top_of_window_long_keys). The
-// contract guard below poisons a row whose sum overflows. bf16 P has the fp32 exponent range.
-constexpr float kTop = 96.f;        // zero / fixed shift: largest exponent a term may reach
-constexpr float kMaxBound = 98.f;   // fixed shift: largest score bound b (smallest row-max term 2^(96 - 2 b) >= 2^-100)
-constexpr float kPDrop = 60.f;      // fixed shift (round 6): rows shift by floor(min(b_row + 60, 126 - b_row)), so
-                                    // P <= 2^-59 where b_row <= 33 and P <= 2^(2 b_row - 125) past it, the row's
-                                    // largest term >= 2^-126. Small P runs the power-limited loop faster (P <= 2 vs
-                                    // 2^17: -0.8 %; 2^-59 vs 2: -0.7 %, profiles/r6/shift_power/)
-constexpr float kGateFixed = 110.f; // gated pair: a block whose data-tight bound is <= 110 runs the fixed shift, whose
-                                    // rows then keep P <= 2^(2 * 110 - 125) = 2^95 (inside the zero-shift window's 2^96)
-constexpr float kTopF8 = 60.f;      // fp8 Q K^T form: P = exp2(S) unshifted for bound products up to this
-constexpr float kLazy = 24.f;       // online max: rescale only when a row max exceeds the shift by more (P <= 2^24)
+// kD, kQBlk, kKBlk, kThreads and the softmax-shift ranges (kTop .. kLazy): attn_route.h, where the routing reads them
+static_assert(kQBlk == kWaves * kQRows && kThreads == kWaves * 64, "attn_route.h's launch geometry");
 
 typedef __attribute__((address_space(3))) const char* lds_char_ptr;
 
@@ -133,6 +117,5 @@ constexpr int kLds16 = 2 * kKBuf16 + 2 * kVBuf16;  // 73728
 // 1 zero shift) and symbol (tail segments separate in profiles); nullptr where that form is not built
 typedef void (*AttnKernel)(AttnArgs);
 AttnKernel wq_kernel(int rows, int mode, bool tail);
-constexpr int kWqThreads = 256;  // 4 waves, one per SIMD
 
 }  // namespace cp25attn

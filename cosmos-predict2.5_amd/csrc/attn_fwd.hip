@@ -6,7 +6,7 @@
 //
 // Three kernels:
 //   attn_fwd_wq   (attn_wide.hip, round 13) long-key self-attention launches in the fixed-shift mode: one wave per SIMD,
-//                 320 / 384 query rows per workgroup, bit-identical per row to attn_fwd_m16 (routing: wide_rows below).
+//                 320 / 384 query rows per workgroup, bit-identical per row to attn_fwd_m16 (routing: attn_route.h).
 //   attn_fwd_m16  every bf16 form. 8 waves x 32 query rows of one (b, h) per workgroup, v_mfma_f32_16x16x32_bf16,
 //                 ping-pong of the two waves of a SIMD (one runs its MFMA phase while the other runs its softmax),
 //                 K/V 64-key tiles double-buffered in padded LDS rows, counted-lgkmcnt operand ring, row sums by
@@ -56,13 +56,13 @@ using namespace cp25attn;
 //   zero   (pre-scaled q, bound product b <= 96): no shift; terms in [2^-b, 2^b];
 //   fixed  (b <= 98; long keys b <= 110, round 6): from the row's own |q_row|: shift floor(min(b_row + 60,
 //          126 - b_row)): P <= 2^-59 where b_row <= 33, P <= 2^(2 b_row - 125) past it, the row's largest term
-//          >= 2^-126 (kPDrop in attn_common.h);
+//          >= 2^-126 (kPDrop in attn_route.h);
 //   online (larger or unknown bounds): tile 0 sets the shift to the row max; a later tile rescales O and the row sum
 //          (and moves the shift) only for a row whose max exceeds the shift by more than kLazy (24), so P <= 2^24 and
 //          the row's largest term >= 1. Per tile: 16 v_max3 per lane and one ballot; the row reduction (two row swaps)
 //          and the rescale run only when a lane's own tile max crosses the threshold (rare after tile 0; rows below it
 //          take the branch with d = 0, exactly, so rows stay independent of each other).
-// The host picks the mode from the bounds (m16_mode).
+// The host picks the mode from the bounds (attn_route.h's attn_route, which the launch and cp25_attn_kernel share).
 // MFMA phase: operand pairs read ahead of their MFMAs (attn_fwd_m16's kAhead): 3 (a ring of 4 fragments) in the
 // per-block forms, 2 in the persistent cross-attention. Round 3 (register-path staging): 2 freed the 4 VGPRs the online
 // form spilled in its loop at 3 (-3.4 %), zero shift -0.1 %, 4: online +7 % (profiles/r3/attn_nop/ring_depth_ab.log,
@@ -1278,145 +1278,61 @@ int num_cus() {
   return g_num_cus;
 }
 
-// Work-balance model for the key-range split: the kernel holds one workgroup per CU (2 waves/SIMD), every
-// workgroup's time is ~ its key tiles + a fixed ~44 tiles, and workgroups run in ceil(nwg / CUs) rounds; a split
-// adds the fp32 partial write + merge traffic (~1 tile of time per 9 MB at HBM rate). The fixed cost is fitted to
-// MI355X measurements (tools/bench_cp_chunks.py: B 2, H 16, Lq 13640, Lk 109120 ran 21.9 ms unsplit vs 23.0 ms at
-// split 4; H 4: 6.24 vs 6.14 ms): shorter workgroups lose the lock-step K/V streaming through the XCD's L2 that
-// long ones keep. Picks the split with the least modelled time.
-// Cost of one split launch in tile-times (a workgroup's prologue / epilogue ~ 44 tiles; the fp32 partials' write,
-// read and merge at ~9 MB per tile-time): the plan's model.
-double split_cost(int64_t nwg, int64_t ntiles, int s, int64_t rows, int64_t cus) {
-  const int64_t tps = cdiv(ntiles, s);
-  double cost = (double)cdiv(nwg * s, cus) * (double)(tps + 44);
-  if (s > 1) cost += (2.0 * s + 0.5) * (double)rows * kD * 4 / 9.0e6;
-  return cost;
-}
-
-// Tail split of an unsplit self-attention launch. With nwg workgroups of equal length on cus CUs the last round runs
-// r = nwg % cus of them and leaves the other CUs idle for a whole workgroup time (the metric launch: 13 664 = 53 x 256
-// + 96, 1.2 % of the launch; a CP = 8 lane: 864 = 3 x 256 + 96, 11 %). The main launch then covers the first nwg - r
-// tiles (whole rounds) and the last r query blocks run as key-range splits (per (b, h) segment, s splits each chosen
-// to fill one round) with their partials merged, which shortens the tail round to ~1/s of a workgroup. TailSeg lists
-// the segments; returns their count (0: no tail split), the largest segment's workspace in *ws_need.
-struct TailSeg { int bh, qb_lo, nblk, s; };
-constexpr int kMaxTailSegs = 4;
-int plan_tail(int B, int H, int Lq, int Lk, int qblk, TailSeg* seg, size_t* ws_need, double* saved) {
-  const int64_t nqb = cdiv(Lq, qblk), ntiles = cdiv(Lk, kKBlk);
-  const int64_t nwg = nqb * B * H, cus = num_cus();
-  const int64_t r = nwg % cus;
-  *ws_need = 0;
-  if (saved) *saved = 0.0;
-  if (r == 0 || nwg < cus || Lk <= 4096) return 0;
-  int n = 0;
-  double cost = 0.0;
-  size_t need = 0;
-  for (int64_t t = nwg - r; t < nwg;) {  // tiles in (b, h) > query block order
-    const int bh = (int)(t / nqb), qb = (int)(t % nqb);
-    const int nblk = (int)std::min<int64_t>(nqb - qb, nwg - t);
-    if (n == kMaxTailSegs) return 0;
-    const int64_t rows = std::min<int64_t>(Lq, (int64_t)(qb + nblk) * qblk) - (int64_t)qb * qblk;
-    int s = 1;
-    for (int c = 2; c <= 8 && c <= ntiles; ++c) {  // the most splits that still fit one round
-      const int64_t tps = cdiv(ntiles, c);
-      if (cdiv(ntiles, tps) == c && (int64_t)nblk * c <= cus) s = c;
-    }
-    if (s == 1 && qblk != kQBlk) {
-      // attn_fwd_wq (round 13): a segment too long for one round of splits (the metric launch's last round is 160
-      // workgroups of one (b, h) at either width) runs as the split count whose rounds of shorter workgroups cost the
-      // least (160 x 3 = 480 workgroups: two rounds of a third each). attn_fwd_m16's launches keep the one-round rule,
-      // so their plans, and with them which rows are merged partials, are what they were.
-      double best = 1e300;
-      for (int c = 2; c <= 8 && c <= ntiles; ++c) {
-        const int64_t tps = cdiv(ntiles, c);
-        if (cdiv(ntiles, tps) != c) continue;
-        const double cc = split_cost(nblk, ntiles, c, rows, cus);
-        if (cc < best) { best = cc; s = c; }
-      }
-    }
-    if (s == 1) return 0;
-    seg[n++] = TailSeg{bh, qb, nblk, s};
-    cost += split_cost(nblk, ntiles, s, rows, cus) + 8.0;  // + launch overhead of the split and merge kernels
-    need = std::max<size_t>(need, (size_t)s * rows * (kD + 1) * sizeof(float));
-    t += nblk;
-  }
-  const double unsplit = (double)(ntiles + 44);  // the tail round as one round of whole workgroups
-  if (cost >= 0.9 * unsplit) return 0;
-  // the multi-round segments above: only where the model recovers at least 0.5 % of the launch
-  if (qblk != kQBlk && unsplit - cost < 0.005 * (double)cdiv(nwg, cus) * unsplit) return 0;
-  *ws_need = need;
-  if (saved) *saved = unsplit - cost;
-  return n;
-}
-
-int plan_split(int B, int H, int Lq, int Lk, int qblk) {
-  const int64_t nqb = cdiv(Lq, qblk), ntiles = cdiv(Lk, kKBlk);
-  const int64_t nwg = nqb * B * H, cus = num_cus();
-  const int64_t rows = (int64_t)B * H * Lq;
-  int best = 1;
-  double best_cost = 1e300;
-  for (int s = 1; s <= 8 && s <= ntiles; ++s) {
-    const int64_t tps = cdiv(ntiles, s);
-    if (cdiv(ntiles, tps) != s) continue;  // every split must own at least one tile
-    double cost = split_cost(nwg, ntiles, s, rows, cus);
-    if (s == 1) {  // unsplit launches may run their last round as a tail split (plan_tail)
-      TailSeg seg[kMaxTailSegs];
-      size_t need;
-      double saved;
-      if (plan_tail(B, H, Lq, Lk, qblk, seg, &need, &saved) > 0) cost -= saved;
-    }
-    if (cost < best_cost * 0.995) { best_cost = cost; best = s; }
-  }
-  return best;
-}
-
-// The m16 softmax-shift mode for these bounds (the bound product in log2 units; |q_row| <= q_norm_bound): 1 zero
-// shift (pre-scaled q, product <= 96), 0 fixed per-row shift (product <= 98), 2 online max (larger or unknown).
-// whole_ok (long-key self-attention launches, round 6): a product <= kGateFixed (110) takes the fixed mode, whose rows
-// then shift by their whole bound to b_row 63 (P <= 2) and by floor(126 - b_row) past it (P <= 2^95): small P, measured
-// 0.8 % faster than the zero shift at the metric launch, the same cycles at a higher power-limited clock
-// (profiles/r6/shift_power/). Short-key launches keep the zero shift (the persistent cross-attention has no fixed mode).
-int m16_mode(float q_norm_bound, float k_norm_bound, float scale_log2, bool prescaled, bool whole_ok = false) {
-  const double bb = (double)q_norm_bound * k_norm_bound * (prescaled ? 1.0 : scale_log2);
-  if (!(q_norm_bound > 0.f && k_norm_bound > 0.f)) return 2;
-  if (whole_ok && bb <= kGateFixed) return 0;
-  if (bb > kMaxBound) return 2;
-  return prescaled && bb <= kTop ? 1 : 0;
-}
-
-// The gated pair (k-norm slots given) runs where the weight bounds alone would leave the launch on the online max
-// (long keys: past kGateFixed; short keys: past the zero-shift window)
-bool m16_gated(float q_norm_bound, float k_norm_bound, bool long_keys) {
-  return long_keys ? m16_mode(q_norm_bound, k_norm_bound, 1.f, true, true) == 2
-                   : m16_mode(q_norm_bound, k_norm_bound, 1.f, true) != 1;
-}
-
-// Short-key (text cross-attention) launches: 1 = the persistent form (attn_fwd_m16<.., kPersist>), 0 = one workgroup
-// per block. Set only through cp25_attn_cross_select (never read from the environment).
+// The two process-wide forms attn_route takes as values (attn_route.h's AttnQuery). g_self_form, long-key
+// self-attention launches (round 13): 0 = attn_fwd_m16 everywhere, 1 = the library's routing to
+// attn_fwd_wq, 320 / 384 = that width wherever attn_fwd_wq supports the launch. g_xattn_form, short-key (text
+// cross-attention) launches: 1 = the persistent form (attn_fwd_m16<.., kPersist>), 0 = one workgroup per block. Set
+// only through cp25_attn_self_select / cp25_attn_cross_select (never read from the environment) and read only by
+// route_query below.
+int g_self_form = 1;
 int g_xattn_form = 1;
 
-// Long-key self-attention launches (round 13): attn_fwd_wq (attn_wide.hip), one wave per SIMD and
-// 320 or 384 query rows per workgroup, for prescaled, ungated bf16 launches with Lk > 4096 in the fixed-shift mode (the
-// mode of every long-key launch with usable bounds); bit-identical per row to attn_fwd_m16. g_self_form: 0 =
-// attn_fwd_m16 everywhere, 1 = the library's routing (wq_default_rows), 320 / 384 = that width wherever attn_fwd_wq
-// supports the launch. Set only through cp25_attn_self_select (never read from the environment). The routing depends
-// only on what cp25_attn_kernel is given, so the name it reports is the kernel that runs.
-// The library's width: 384 rows, measured -7.4 % per launch against attn_fwd_m16 at the metric launch (320: -5.0 %)
-// and -8.8 % at a CP = 8 rank's 13 640 x 109 120 (320: -5.5 %); up to 8192 keys 320 rows, which at config 5's
-// L = 4800 measured -15 % against -6 % for 384 (its 480 shorter workgroups fill the second round better than 416
-// longer ones). profiles/r13/attn_wide/SUMMARY.md.
-int wq_default_rows(int Lk) { return Lk > 8192 ? 384 : 320; }
-int g_self_form = 1;
-// query rows per workgroup of the wide kernel for this launch, or 0: attn_fwd_m16 (256)
-int wide_rows(bool prescaled, int fp8, bool gated, int Lk, int mode) {
-  if (g_self_form == 0 || !prescaled || fp8 != 0 || gated || Lk <= 4096 || mode == 2) return 0;
-  const int rows = g_self_form == 1 ? wq_default_rows(Lk) : g_self_form;
-  return wq_kernel(rows, mode, false) ? rows : 0;
+// the attn_fwd_wq forms attn_wide.hip built, as attn_route reads them
+unsigned wide_built() {
+  unsigned m = 0;
+  for (int rows : {320, 384})
+    for (int mode : {0, 1})
+      if (wq_kernel(rows, mode, false)) m |= wide_bit(rows, mode);
+  return m;
 }
 
-// the persistent form runs unsplit cross-attention launches in the zero-shift and online modes with >= 2 key tiles
-bool use_xattn_persistent(bool short_keys, int n_split, int mode, int64_t ntiles) {
-  return g_xattn_form == 1 && short_keys && n_split == 1 && mode != 0 && ntiles >= 2;
+AttnQuery route_query(int Lk, bool prescaled, float softmax_scale, float q_norm_bound, float k_norm_bound, int fp8,
+                      bool has_kslots, bool has_qnorm, int n_split) {
+  return AttnQuery{Lk, prescaled, prescaled ? 1.f : softmax_scale * 1.4426950408889634f, q_norm_bound, k_norm_bound,
+                   fp8, has_kslots, has_qnorm, n_split, g_self_form, g_xattn_form, wide_built()};
+}
+
+// The kernels of a route. tail: the same code as a separate symbol for the tail-split segments (plan_tail:
+// self-attention shapes only, so the plain forms alone have one).
+template <bool kPre, int kMode>
+AttnKernel m16_plain(bool cross, bool tail) {
+  if (tail) return attn_fwd_m16<0, kPre, kMode, false, 0, 1>;
+  return cross ? attn_fwd_m16<1, kPre, kMode> : attn_fwd_m16<0, kPre, kMode>;
+}
+AttnKernel m16_kernel(const AttnRoute& r, bool tail) {
+  const bool cross = r.kind == AttnKind::cross;
+  if (r.gated) return cross ? attn_fwd_m16<1, true, 2, false, 2> : attn_fwd_m16<0, true, 2, false, 2>;
+  if (r.persistent) {
+    if (!r.prescaled) return attn_fwd_m16<1, false, 2, true>;
+    return r.mode == 2 ? attn_fwd_m16<1, true, 2, true> : attn_fwd_m16<1, true, 1, true>;
+  }
+  if (!r.prescaled) return r.mode == 2 ? m16_plain<false, 2>(cross, tail) : m16_plain<false, 0>(cross, tail);
+  return r.mode == 2 ? m16_plain<true, 2>(cross, tail)
+                     : (r.mode == 1 ? m16_plain<true, 1>(cross, tail) : m16_plain<true, 0>(cross, tail));
+}
+// the gated pair's first launch: blocks whose data-tight bound allows it (<= kGateFixed) run the fixed-shift loop with
+// the measured key bound, the others the online max of m16_kernel's
+AttnKernel m16_gate_fixed_kernel(const AttnRoute& r) {
+  return r.kind == AttnKind::cross ? attn_fwd_m16<1, true, 0, false, 1> : attn_fwd_m16<0, true, 0, false, 1>;
+}
+AttnKernel f8_kernel(const AttnRoute& r) {
+  const bool cross = r.kind == AttnKind::cross;
+  if (r.f8 == 3) return cross ? attn_fwd_f8<1, 3> : attn_fwd_f8<0, 3>;
+  return cross ? attn_fwd_f8<1, 1> : attn_fwd_f8<0, 1>;
+}
+AttnKernel route_kernel(const AttnRoute& r, bool tail) {
+  if (r.family == AttnFamily::f8) return f8_kernel(r);
+  return r.family == AttnFamily::wq ? wq_kernel(r.rows, r.mode, tail) : m16_kernel(r, tail);
 }
 
 }  // namespace
@@ -1446,89 +1362,104 @@ extern "C" void cp25_attn_probe_set(unsigned long long* probe, int t0, int n_wg)
 }
 #endif
 
-// fp8: 0 bf16; 1 = Q K^T on e4m3 q / k; 2 = also P.V on e5m2 P and the e4m3 v8t layout (v = v8t, v_strides unused)
-static int attn_launch(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq, int Lk, int D,
-                       const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                       const int64_t* o_strides, float softmax_scale, float q_norm_bound, float k_norm_bound,
-                       int n_split, void* workspace, size_t ws_bytes, hipStream_t stream, bool prescaled = false,
-                       int fp8 = 0, const float* v_amax = nullptr, const float* kslots = nullptr, int n_kslots = 0,
-                       const AttnArgs* qn = nullptr) {
+// One launch as the entry points below describe it; a field an entry point leaves out is zero.
+struct AttnCall {
+  const void *q, *k, *v;
+  void* o;
+  int B, H, Lq, Lk, D;
+  const int64_t *q_strides, *k_strides, *v_strides, *o_strides;
+  float softmax_scale, q_norm_bound, k_norm_bound;
+  int n_split;
+  void* workspace;
+  size_t ws_bytes;
+  hipStream_t stream;
+  bool prescaled;
+  int fp8;  // 0 bf16; 1 = Q K^T on e4m3 q / k; 2 = also P.V on e5m2 P and the e4m3 v8t layout (v = v8t, no v_strides)
+  const float* v_amax;
+  const float* kslots;
+  int n_kslots;
+  const void* qn_w;  // in-kernel q normalisation (AttnArgs's qn_*); nullptr: none
+  const float *qn_cos, *qn_sin;
+  float qn_eps, qn_scale;
+};
+
+static int attn_launch(const AttnCall& c) {
+  const int B = c.B, H = c.H, Lq = c.Lq, Lk = c.Lk, fp8 = c.fp8, n_split = c.n_split;
+  const float q_norm_bound = c.q_norm_bound, k_norm_bound = c.k_norm_bound;
   const bool fp8qk = fp8 >= 1;
-  if (D != kD) return CP25_ERR_DTYPE;
-  if (fp8qk && !prescaled) return CP25_ERR_INVAL;
-  if (fp8 == 2 && (!v_amax || ((uintptr_t)v_amax & 3))) return CP25_ERR_INVAL;
+  if (c.D != kD) return CP25_ERR_DTYPE;
+  if (fp8qk && !c.prescaled) return CP25_ERR_INVAL;
+  if (fp8 == 2 && (!c.v_amax || ((uintptr_t)c.v_amax & 3))) return CP25_ERR_INVAL;
   // fp8 Q K^T: P = exp2(S) with no shift needs every score inside [-60, 60]
   if (fp8qk && !(q_norm_bound > 0.f && k_norm_bound > 0.f && (double)q_norm_bound * k_norm_bound <= (double)kTopF8))
     return CP25_ERR_INVAL;
   // fp8 P.V: the e5m2 window [2^-15, 2^15] must hold a term of every row (shift 1.13 qb kb - 15 <= 15)
-  if (fp8 == 2 && 1.13 * (double)q_norm_bound * k_norm_bound > 30.0) return CP25_ERR_INVAL;
+  if (fp8 == 2 && kF8Round * (double)q_norm_bound * k_norm_bound > kF8PvSpan) return CP25_ERR_INVAL;
   if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return CP25_ERR_INVAL;
-  if (!q || !k || !v || !o) return CP25_ERR_INVAL;
-  if (!(softmax_scale > 0.f) || !(q_norm_bound >= 0.f) || !(k_norm_bound >= 0.f) || q_norm_bound > 1e18f ||
+  if (!c.q || !c.k || !c.v || !c.o) return CP25_ERR_INVAL;
+  if (!(c.softmax_scale > 0.f) || !(q_norm_bound >= 0.f) || !(k_norm_bound >= 0.f) || q_norm_bound > 1e18f ||
       k_norm_bound > 1e18f)
     return CP25_ERR_INVAL;
   // rows must be 16-byte aligned for the vector loads / stores; head dim contiguous
-  const int64_t* ss[4] = {q_strides, k_strides, v_strides, o_strides};
+  const int64_t* ss[4] = {c.q_strides, c.k_strides, c.v_strides, c.o_strides};
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 3; ++j)
       if (!(fp8 == 2 && i == 2) && ss[i][j] % (fp8qk && i < 2 ? 16 : 8) != 0) return CP25_ERR_INVAL;
   // buffer_load offsets within a 64-key tile are 32-bit
-  if ((int64_t)kKBlk * k_strides[1] * (fp8qk ? 1 : 2) >= (1ll << 31) ||
-      (fp8 != 2 && (int64_t)kKBlk * v_strides[1] * 2 >= (1ll << 31)))
+  if ((int64_t)kKBlk * c.k_strides[1] * (fp8qk ? 1 : 2) >= (1ll << 31) ||
+      (fp8 != 2 && (int64_t)kKBlk * c.v_strides[1] * 2 >= (1ll << 31)))
     return CP25_ERR_INVAL;
-  if (k_strides[1] <= 0 || (fp8 != 2 && v_strides[1] <= 0)) return CP25_ERR_INVAL;
-  if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) & 15) return CP25_ERR_INVAL;
+  if (c.k_strides[1] <= 0 || (fp8 != 2 && c.v_strides[1] <= 0)) return CP25_ERR_INVAL;
+  if (((uintptr_t)c.q | (uintptr_t)c.k | (uintptr_t)c.v | (uintptr_t)c.o) & 15) return CP25_ERR_INVAL;
   const int64_t ntiles = cdiv(Lk, kKBlk);
   if (n_split < 1 || n_split > ntiles) return CP25_ERR_INVAL;
   const int64_t tps = cdiv(ntiles, n_split);
   if (cdiv(ntiles, tps) != n_split) return CP25_ERR_INVAL;  // a split without keys
   const int64_t rows = (int64_t)B * H * Lq;
   if (n_split > 1) {
-    if (!workspace || ((uintptr_t)workspace & 15) || ws_bytes < cp25_attn_workspace_bytes(B, H, Lq, n_split))
+    if (!c.workspace || ((uintptr_t)c.workspace & 15) || c.ws_bytes < cp25_attn_workspace_bytes(B, H, Lq, n_split))
       return CP25_ERR_INVAL;
   }
+  const AttnQuery query = route_query(Lk, c.prescaled, c.softmax_scale, q_norm_bound, k_norm_bound, fp8,
+                                      c.kslots != nullptr, c.qn_w != nullptr, n_split);
+  const AttnRoute route = attn_route(query);
+  const int qblk = route.rows;  // query rows per workgroup
+  const int64_t cus = num_cus();
   // unsplit self-attention with a workspace (cp25_attn_tail_workspace_bytes): the last, partial round as a tail split
-  const bool xk = Lk <= 4096;  // short-key launches (text cross-attention) get their own symbol in profiles
-  const float sl2 = prescaled ? 1.f : softmax_scale * 1.4426950408889634f;
-  const int mode = m16_mode(q_norm_bound, k_norm_bound, sl2, prescaled, !xk);
-  const bool gated = prescaled && kslots && m16_gated(q_norm_bound, k_norm_bound, !xk);
-  // query rows per workgroup: attn_fwd_m16's 256, or the wide kernel's where the launch is routed to it
-  const int wq_rows = wide_rows(prescaled, fp8, gated, Lk, mode);
-  const int qblk = wq_rows ? wq_rows : kQBlk;
   TailSeg tail[kMaxTailSegs];
   int n_tail = 0;
-  if (n_split == 1 && fp8 == 0 && !kslots && workspace && !((uintptr_t)workspace & 15)) {
+  if (n_split == 1 && fp8 == 0 && !c.kslots && c.workspace && !((uintptr_t)c.workspace & 15)) {
     size_t need = 0;
-    n_tail = plan_tail(B, H, Lq, Lk, qblk, tail, &need, nullptr);
-    if (ws_bytes < need) n_tail = 0;
+    n_tail = plan_tail(B, H, Lq, Lk, qblk, cus, tail, &need, nullptr);
+    if (c.ws_bytes < need) n_tail = 0;
   }
   AttnArgs a;
-  a.q = (const unsigned short*)q; a.k = (const unsigned short*)k; a.v = (const unsigned short*)v;
-  a.o = (unsigned short*)o;
-  a.q_sb = q_strides[0]; a.q_sl = q_strides[1]; a.q_sh = q_strides[2];
-  a.k_sb = k_strides[0]; a.k_sl = k_strides[1]; a.k_sh = k_strides[2];
-  a.v_sb = v_strides[0]; a.v_sl = v_strides[1]; a.v_sh = v_strides[2];
-  a.o_sb = o_strides[0]; a.o_sl = o_strides[1]; a.o_sh = o_strides[2];
+  a.q = (const unsigned short*)c.q; a.k = (const unsigned short*)c.k; a.v = (const unsigned short*)c.v;
+  a.o = (unsigned short*)c.o;
+  a.q_sb = c.q_strides[0]; a.q_sl = c.q_strides[1]; a.q_sh = c.q_strides[2];
+  a.k_sb = c.k_strides[0]; a.k_sl = c.k_strides[1]; a.k_sh = c.k_strides[2];
+  a.v_sb = c.v_strides[0]; a.v_sl = c.v_strides[1]; a.v_sh = c.v_strides[2];
+  a.o_sb = c.o_strides[0]; a.o_sl = c.o_strides[1]; a.o_sh = c.o_strides[2];
   a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk;
   a.nqb = (int)cdiv(Lq, qblk);
   a.nsplit = n_split;
   a.tps = (int)tps;
   a.ntk_v = (int)ntiles;
-  a.v_amax = v_amax;
+  a.v_amax = c.v_amax;
   // fp8 P.V: P = exp2(S - shift) <= 2^15 (e5m2 max 57344 = 2^15.8) for every score the norm bounds allow, with the
-  // e4m3 rounding of q and k (each element within 2^-4 relative: |q8| |k8| <= 1.13 |q| |k|)
-  a.s_init = fp8 == 2 ? -std::max(0.f, 1.13f * q_norm_bound * k_norm_bound - 15.f) : 0.f;
-  a.o_part = n_split > 1 ? (float*)workspace : nullptr;
-  a.lse_part = n_split > 1 ? (float*)workspace + (size_t)n_split * rows * kD : nullptr;
-  a.scale_log2 = sl2;
+  // e4m3 rounding of q and k (kF8Round)
+  a.s_init = fp8 == 2 ? -std::max(0.f, (float)kF8Round * q_norm_bound * k_norm_bound - 15.f) : 0.f;
+  a.o_part = n_split > 1 ? (float*)c.workspace : nullptr;
+  a.lse_part = n_split > 1 ? (float*)c.workspace + (size_t)n_split * rows * kD : nullptr;
+  a.scale_log2 = query.scale_log2;
   a.kbound = q_norm_bound > 0.f ? k_norm_bound : 0.f;  // a missing q bound: online (the kernel measures |q_row|)
-  a.kslots = kslots;
-  a.n_kslots = n_kslots;
-  a.qn_w = qn ? qn->qn_w : nullptr;
-  a.qn_cos = qn ? qn->qn_cos : nullptr;
-  a.qn_sin = qn ? qn->qn_sin : nullptr;
-  a.qn_eps = qn ? qn->qn_eps : 0.f;
-  a.qn_scale = qn ? qn->qn_scale : 1.f;
+  a.kslots = c.kslots;
+  a.n_kslots = c.n_kslots;
+  a.qn_w = (const unsigned short*)c.qn_w;
+  a.qn_cos = c.qn_cos;
+  a.qn_sin = c.qn_sin;
+  a.qn_eps = c.qn_eps;
+  a.qn_scale = c.qn_w ? c.qn_scale : 1.f;
   a.qn_row0 = 0;
 #ifdef CP25_ATTN_PROBE
   a.probe = g_probe;
@@ -1537,87 +1468,64 @@ static int attn_launch(const void* q, const void* k, const void* v, void* o, int
 #endif
   const int64_t nwg = (int64_t)a.nqb * B * H * n_split;
   if (nwg > 0x7fffffff) return CP25_ERR_INVAL;
-  if (fp8 == 2) {
-    hipLaunchKernelGGL((xk ? attn_fwd_f8<1, 3> : attn_fwd_f8<0, 3>), dim3((unsigned)nwg), dim3(kThreads), 0, stream, a);
-  } else if (fp8qk) {
-    hipLaunchKernelGGL((xk ? attn_fwd_f8<1, 1> : attn_fwd_f8<0, 1>), dim3((unsigned)nwg), dim3(kThreads), 0, stream, a);
-  } else {
-    void (*kern)(AttnArgs) = nullptr;
-    void (*kern_tail)(AttnArgs) = nullptr;  // the tail segments' symbol (plan_tail: self-attention shapes only)
-    int64_t grid = nwg;
-    int threads = kThreads;
-    if (gated) {
-      // the gated pair: blocks whose data-tight bound allows it (<= kGateFixed) run the fixed-shift loop with the
-      // measured key bound, the others the online max
-      hipLaunchKernelGGL((xk ? attn_fwd_m16<1, true, 0, false, 1> : attn_fwd_m16<0, true, 0, false, 1>),
-                         dim3((unsigned)nwg), dim3(kThreads), 0, stream, a);
-      CP25_LAUNCH_CHECK();
-      kern = xk ? attn_fwd_m16<1, true, 2, false, 2> : attn_fwd_m16<0, true, 2, false, 2>;
-    } else if (!qn && use_xattn_persistent(xk, n_split, mode, ntiles)) {  // (its Q path has no normalisation)
-      // one workgroup per CU over contiguous runs of blocks (every workgroup gets at least one)
-      grid = std::min<int64_t>(nwg, num_cus());
-      if (prescaled) kern = mode == 2 ? attn_fwd_m16<1, true, 2, true> : attn_fwd_m16<1, true, 1, true>;
-      else kern = attn_fwd_m16<1, false, 2, true>;
-    } else {
-#define M16(P, M) kern = xk ? attn_fwd_m16<1, P, M> : attn_fwd_m16<0, P, M>; \
-                  kern_tail = attn_fwd_m16<0, P, M, false, 0, 1>
-      if (wq_rows) {
-        kern = wq_kernel(wq_rows, mode, false);
-        kern_tail = wq_kernel(wq_rows, mode, true);
-        threads = kWqThreads;
-      } else if (prescaled) {
-        if (mode == 2) { M16(true, 2); } else if (mode == 1) { M16(true, 1); } else { M16(true, 0); }
-      } else {
-        if (mode == 2) { M16(false, 2); } else { M16(false, 0); }
-      }
-#undef M16
-      if (n_tail) grid = nwg - nwg % num_cus();  // whole rounds; the rest below
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(threads), 0, stream, a);
+  const dim3 threads(route.threads);
+  int64_t grid = nwg;
+  if (route.gated) {
+    hipLaunchKernelGGL(m16_gate_fixed_kernel(route), dim3((unsigned)nwg), threads, 0, c.stream, a);
     CP25_LAUNCH_CHECK();
-    // tail segments: (b, h) = bh, query blocks [qb_lo, qb_lo + nblk), as a B = H = 1 problem of s key-range splits on
-    // the same kernel, its fp32 partials in the workspace, merged into o (the same arithmetic as any split launch)
-    for (int i = grid < nwg ? 0 : n_tail; i < n_tail; ++i) {
-      const TailSeg& g = tail[i];
-      const int b = g.bh / H, h = g.bh % H;
-      const int64_t row0 = (int64_t)g.qb_lo * qblk;
-      AttnArgs t = a;
-      t.q = a.q + b * a.q_sb + h * a.q_sh + row0 * a.q_sl;
-      t.k = a.k + b * a.k_sb + h * a.k_sh;
-      t.v = a.v + b * a.v_sb + h * a.v_sh;
-      t.o = a.o + b * a.o_sb + h * a.o_sh + row0 * a.o_sl;
-      t.B = 1; t.H = 1;
-      t.Lq = (int)(std::min<int64_t>(Lq, row0 + (int64_t)g.nblk * qblk) - row0);
-      t.qn_row0 = (int)row0;  // the sub-problem's query row 0 is token row0 (RoPE tables)
-      t.nqb = g.nblk;
-      t.nsplit = g.s;
-      t.tps = (int)cdiv(ntiles, g.s);
-      t.o_part = (float*)workspace;
-      t.lse_part = (float*)workspace + (size_t)g.s * t.Lq * kD;
-      hipLaunchKernelGGL(kern_tail, dim3((unsigned)(g.nblk * g.s)), dim3(threads), 0, stream, t);
-      CP25_LAUNCH_CHECK();
-      hipLaunchKernelGGL(attn_merge_splits, dim3((unsigned)cdiv((int64_t)t.Lq * 32, 256)), dim3(256), 0, stream,
-                         t.o_part, t.lse_part, t.o, g.s, 1, 1, t.Lq, a.o_sb, a.o_sl, a.o_sh);
-      CP25_LAUNCH_CHECK();
-    }
+  } else if (route.persistent) {
+    grid = std::min<int64_t>(nwg, cus);  // one workgroup per CU over contiguous runs of blocks (each gets at least one)
+  } else if (n_tail) {
+    grid = nwg - nwg % cus;  // whole rounds; the rest below
   }
+  hipLaunchKernelGGL(route_kernel(route, false), dim3((unsigned)grid), threads, 0, c.stream, a);
   CP25_LAUNCH_CHECK();
+  // tail segments: (b, h) = bh, query blocks [qb_lo, qb_lo + nblk), as a B = H = 1 problem of s key-range splits on
+  // the same kernel, its fp32 partials in the workspace, merged into o (the same arithmetic as any split launch)
+  for (int i = grid < nwg ? 0 : n_tail; i < n_tail; ++i) {
+    const TailSeg& g = tail[i];
+    const int b = g.bh / H, h = g.bh % H;
+    const int64_t row0 = (int64_t)g.qb_lo * qblk;
+    AttnArgs t = a;
+    t.q = a.q + b * a.q_sb + h * a.q_sh + row0 * a.q_sl;
+    t.k = a.k + b * a.k_sb + h * a.k_sh;
+    t.v = a.v + b * a.v_sb + h * a.v_sh;
+    t.o = a.o + b * a.o_sb + h * a.o_sh + row0 * a.o_sl;
+    t.B = 1; t.H = 1;
+    t.Lq = (int)(std::min<int64_t>(Lq, row0 + (int64_t)g.nblk * qblk) - row0);
+    t.qn_row0 = (int)row0;  // the sub-problem's query row 0 is token row0 (RoPE tables)
+    t.nqb = g.nblk;
+    t.nsplit = g.s;
+    t.tps = (int)cdiv(ntiles, g.s);
+    t.o_part = (float*)c.workspace;
+    t.lse_part = (float*)c.workspace + (size_t)g.s * t.Lq * kD;
+    hipLaunchKernelGGL(route_kernel(route, true), dim3((unsigned)(g.nblk * g.s)), threads, 0, c.stream, t);
+    CP25_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attn_merge_splits, dim3((unsigned)cdiv((int64_t)t.Lq * 32, 256)), dim3(256), 0, c.stream,
+                       t.o_part, t.lse_part, t.o, g.s, 1, 1, t.Lq, a.o_sb, a.o_sl, a.o_sh);
+    CP25_LAUNCH_CHECK();
+  }
   if (n_split > 1) {
-    const int64_t threads = rows * 32;
-    hipLaunchKernelGGL(attn_merge_splits, dim3((unsigned)cdiv(threads, 256)), dim3(256), 0, stream, a.o_part,
+    hipLaunchKernelGGL(attn_merge_splits, dim3((unsigned)cdiv(rows * 32, 256)), dim3(256), 0, c.stream, a.o_part,
                        a.lse_part, a.o, n_split, B, H, Lq, a.o_sb, a.o_sl, a.o_sh);
     CP25_LAUNCH_CHECK();
   }
   return CP25_OK;
 }
 
+// log 2: a prescaled launch's nominal softmax_scale (its q rows already carry scale * log2 e)
+constexpr float kLn2 = 0.6931471805599453f;
+
 extern "C" int cp25_attn_fwd_prescaled_fp8qk(const void* q8, const void* k8, const void* v, void* o, int B, int H,
                                              int Lq, int Lk, int D, const int64_t* q_strides,
                                              const int64_t* k_strides, const int64_t* v_strides,
                                              const int64_t* o_strides, float q_norm_bound, float k_norm_bound,
                                              int n_split, void* workspace, size_t ws_bytes, hipStream_t stream) {
-  return attn_launch(q8, k8, v, o, B, H, Lq, Lk, D, q_strides, k_strides, v_strides, o_strides, 0.6931471805599453f,
-                     q_norm_bound, k_norm_bound, n_split, workspace, ws_bytes, stream, true, 1);
+  return attn_launch({.q = q8, .k = k8, .v = v, .o = o, .B = B, .H = H, .Lq = Lq, .Lk = Lk, .D = D,
+                      .q_strides = q_strides, .k_strides = k_strides, .v_strides = v_strides, .o_strides = o_strides,
+                      .softmax_scale = kLn2, .q_norm_bound = q_norm_bound, .k_norm_bound = k_norm_bound,
+                      .n_split = n_split, .workspace = workspace, .ws_bytes = ws_bytes, .stream = stream,
+                      .prescaled = true, .fp8 = 1});
 }
 
 extern "C" int cp25_attn_fwd_prescaled_fp8(const void* q8, const void* k8, const void* v8t, const float* v_amax,
@@ -1626,8 +1534,11 @@ extern "C" int cp25_attn_fwd_prescaled_fp8(const void* q8, const void* k8, const
                                            float k_norm_bound, int n_split, void* workspace, size_t ws_bytes,
                                            hipStream_t stream) {
   const int64_t none[3] = {0, 0, 0};
-  return attn_launch(q8, k8, v8t, o, B, H, Lq, Lk, D, q_strides, k_strides, none, o_strides, 0.6931471805599453f,
-                     q_norm_bound, k_norm_bound, n_split, workspace, ws_bytes, stream, true, 2, v_amax);
+  return attn_launch({.q = q8, .k = k8, .v = v8t, .o = o, .B = B, .H = H, .Lq = Lq, .Lk = Lk, .D = D,
+                      .q_strides = q_strides, .k_strides = k_strides, .v_strides = none, .o_strides = o_strides,
+                      .softmax_scale = kLn2, .q_norm_bound = q_norm_bound, .k_norm_bound = k_norm_bound,
+                      .n_split = n_split, .workspace = workspace, .ws_bytes = ws_bytes, .stream = stream,
+                      .prescaled = true, .fp8 = 2, .v_amax = v_amax});
 }
 
 extern "C" size_t cp25_attn_workspace_bytes(int B, int H, int Lq, int n_split) {
@@ -1637,35 +1548,32 @@ extern "C" size_t cp25_attn_workspace_bytes(int B, int H, int Lq, int n_split) {
 
 extern "C" size_t cp25_attn_tail_workspace_bytes(int B, int H, int Lq, int Lk) {
   if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return 0;
-  // the shape alone does not say which kernel the launch takes (that needs the bounds): enough for either
-  TailSeg seg[kMaxTailSegs];
-  size_t need = 0, best = 0;
-  const int wide = g_self_form == 0 ? 0 : (g_self_form == 1 ? wq_default_rows(Lk) : g_self_form);
-  for (int qblk : {kQBlk, Lk > 4096 ? wide : 0})
-    if (qblk > 0 && plan_tail(B, H, Lq, Lk, qblk, seg, &need, nullptr) > 0) best = std::max(best, need);
-  return best;
+  return tail_workspace_bytes(B, H, Lq, Lk, g_self_form, num_cus());
 }
 
 extern "C" int cp25_attn_plan(int B, int H, int Lq, int Lk, int D) {
   if (D != kD) return CP25_ERR_DTYPE;
   if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0) return CP25_ERR_INVAL;
-  return plan_split(B, H, Lq, Lk, kQBlk);  // (from the shape alone: attn_fwd_m16's query blocks)
+  return plan_split(B, H, Lq, Lk, kQBlk, num_cus());  // (from the shape alone: attn_fwd_m16's query blocks)
 }
 
 extern "C" int cp25_attn_fwd(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
                              int Lk, int D, const int64_t* q_strides, const int64_t* k_strides,
                              const int64_t* v_strides, const int64_t* o_strides, float softmax_scale,
                              hipStream_t stream) {
-  return attn_launch(q, k, v, o, B, H, Lq, Lk, D, q_strides, k_strides, v_strides, o_strides, softmax_scale, 0.f,
-                     0.f, 1, nullptr, 0, stream);
+  return attn_launch({.q = q, .k = k, .v = v, .o = o, .B = B, .H = H, .Lq = Lq, .Lk = Lk, .D = D,
+                      .q_strides = q_strides, .k_strides = k_strides, .v_strides = v_strides, .o_strides = o_strides,
+                      .softmax_scale = softmax_scale, .n_split = 1, .stream = stream});
 }
 
 extern "C" int cp25_attn_fwd_split(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
                                    int Lk, int D, const int64_t* q_strides, const int64_t* k_strides,
                                    const int64_t* v_strides, const int64_t* o_strides, float softmax_scale,
                                    int n_split, void* workspace, size_t ws_bytes, hipStream_t stream) {
-  return attn_launch(q, k, v, o, B, H, Lq, Lk, D, q_strides, k_strides, v_strides, o_strides, softmax_scale, 0.f,
-                     0.f, n_split, workspace, ws_bytes, stream);
+  return attn_launch({.q = q, .k = k, .v = v, .o = o, .B = B, .H = H, .Lq = Lq, .Lk = Lk, .D = D,
+                      .q_strides = q_strides, .k_strides = k_strides, .v_strides = v_strides, .o_strides = o_strides,
+                      .softmax_scale = softmax_scale, .n_split = n_split, .workspace = workspace,
+                      .ws_bytes = ws_bytes, .stream = stream});
 }
 
 extern "C" int cp25_attn_fwd_bounded(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
@@ -1673,8 +1581,10 @@ extern "C" int cp25_attn_fwd_bounded(const void* q, const void* k, const void* v
                                      const int64_t* v_strides, const int64_t* o_strides, float softmax_scale,
                                      float q_norm_bound, float k_norm_bound, int n_split, void* workspace,
                                      size_t ws_bytes, hipStream_t stream) {
-  return attn_launch(q, k, v, o, B, H, Lq, Lk, D, q_strides, k_strides, v_strides, o_strides, softmax_scale,
-                     q_norm_bound, k_norm_bound, n_split, workspace, ws_bytes, stream);
+  return attn_launch({.q = q, .k = k, .v = v, .o = o, .B = B, .H = H, .Lq = Lq, .Lk = Lk, .D = D,
+                      .q_strides = q_strides, .k_strides = k_strides, .v_strides = v_strides, .o_strides = o_strides,
+                      .softmax_scale = softmax_scale, .q_norm_bound = q_norm_bound, .k_norm_bound = k_norm_bound,
+                      .n_split = n_split, .workspace = workspace, .ws_bytes = ws_bytes, .stream = stream});
 }
 
 extern "C" int cp25_attn_fwd_prescaled(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
@@ -1682,8 +1592,11 @@ extern "C" int cp25_attn_fwd_prescaled(const void* q, const void* k, const void*
                                        const int64_t* v_strides, const int64_t* o_strides, float q_norm_bound,
                                        float k_norm_bound, int n_split, void* workspace, size_t ws_bytes,
                                        hipStream_t stream) {
-  return attn_launch(q, k, v, o, B, H, Lq, Lk, D, q_strides, k_strides, v_strides, o_strides, 0.6931471805599453f,
-                     q_norm_bound, k_norm_bound, n_split, workspace, ws_bytes, stream, true);
+  return attn_launch({.q = q, .k = k, .v = v, .o = o, .B = B, .H = H, .Lq = Lq, .Lk = Lk, .D = D,
+                      .q_strides = q_strides, .k_strides = k_strides, .v_strides = v_strides, .o_strides = o_strides,
+                      .softmax_scale = kLn2, .q_norm_bound = q_norm_bound, .k_norm_bound = k_norm_bound,
+                      .n_split = n_split, .workspace = workspace, .ws_bytes = ws_bytes, .stream = stream,
+                      .prescaled = true});
 }
 
 extern "C" int cp25_attn_fwd_prescaled_kslots(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
@@ -1692,9 +1605,11 @@ extern "C" int cp25_attn_fwd_prescaled_kslots(const void* q, const void* k, cons
                                               float k_norm_bound, const float* k_norm_slots, int n_slots, int n_split,
                                               void* workspace, size_t ws_bytes, hipStream_t stream) {
   if (!k_norm_slots || n_slots < 1 || n_slots > 64 || ((uintptr_t)k_norm_slots & 3)) return CP25_ERR_INVAL;
-  return attn_launch(q, k, v, o, B, H, Lq, Lk, D, q_strides, k_strides, v_strides, o_strides, 0.6931471805599453f,
-                     q_norm_bound, k_norm_bound, n_split, workspace, ws_bytes, stream, true, 0, nullptr, k_norm_slots,
-                     n_slots);
+  return attn_launch({.q = q, .k = k, .v = v, .o = o, .B = B, .H = H, .Lq = Lq, .Lk = Lk, .D = D,
+                      .q_strides = q_strides, .k_strides = k_strides, .v_strides = v_strides, .o_strides = o_strides,
+                      .softmax_scale = kLn2, .q_norm_bound = q_norm_bound, .k_norm_bound = k_norm_bound,
+                      .n_split = n_split, .workspace = workspace, .ws_bytes = ws_bytes, .stream = stream,
+                      .prescaled = true, .kslots = k_norm_slots, .n_kslots = n_slots});
 }
 
 extern "C" int cp25_attn_fwd_prescaled_qnorm(const void* q, const void* k, const void* v, void* o, int B, int H, int Lq,
@@ -1709,47 +1624,18 @@ extern "C" int cp25_attn_fwd_prescaled_qnorm(const void* q, const void* k, const
       !(q_scale > 0.f))
     return CP25_ERR_INVAL;
   if ((((uintptr_t)cos_tab) | ((uintptr_t)sin_tab)) & 15) return CP25_ERR_INVAL;  // read as f32x4 (as cp25_gemm_qkv)
-  AttnArgs qn{};
-  qn.qn_w = (const unsigned short*)q_norm_weight;
-  qn.qn_cos = cos_tab;
-  qn.qn_sin = sin_tab;
-  qn.qn_eps = eps;
-  qn.qn_scale = q_scale;
-  return attn_launch(q, k, v, o, B, H, Lq, Lk, D, q_strides, k_strides, v_strides, o_strides, 0.6931471805599453f,
-                     q_norm_bound, k_norm_bound, n_split, workspace, ws_bytes, stream, true, 0, nullptr, k_norm_slots,
-                     k_norm_slots ? n_slots : 0, &qn);
+  return attn_launch({.q = q, .k = k, .v = v, .o = o, .B = B, .H = H, .Lq = Lq, .Lk = Lk, .D = D,
+                      .q_strides = q_strides, .k_strides = k_strides, .v_strides = v_strides, .o_strides = o_strides,
+                      .softmax_scale = kLn2, .q_norm_bound = q_norm_bound, .k_norm_bound = k_norm_bound,
+                      .n_split = n_split, .workspace = workspace, .ws_bytes = ws_bytes, .stream = stream,
+                      .prescaled = true, .kslots = k_norm_slots, .n_kslots = k_norm_slots ? n_slots : 0,
+                      .qn_w = q_norm_weight, .qn_cos = cos_tab, .qn_sin = sin_tab, .qn_eps = eps, .qn_scale = q_scale});
 }
 
+// The name of the kernel an unsplit launch with these arguments takes (prescaled 2: with k-norm slots, as
+// cp25_attn_fwd_prescaled_kslots): the route attn_launch takes, so the name reported is the kernel that runs.
 extern "C" const char* cp25_attn_kernel(int Lk, float softmax_scale, float q_norm_bound, float k_norm_bound,
                                         int prescaled, int fp8) {
-  if (prescaled == 2 && m16_gated(q_norm_bound, k_norm_bound, Lk > 4096))  // cp25_attn_fwd_prescaled_kslots
-    return Lk <= 4096 ? "attn_fwd_m16<cross, prescaled, gated fixed shift | online max>"
-                      : "attn_fwd_m16<self, prescaled, gated fixed shift | online max>";
-  if (fp8 == 2) return Lk <= 4096 ? "attn_fwd_f8<cross, fp8 Q K^T + fp8 P.V>" : "attn_fwd_f8<self, fp8 Q K^T + fp8 P.V>";
-  if (fp8 == 1) return Lk <= 4096 ? "attn_fwd_f8<cross, fp8 Q K^T>" : "attn_fwd_f8<self, fp8 Q K^T>";
-  if (Lk <= 4096) {
-    const float sl = prescaled ? 1.f : softmax_scale * 1.4426950408889634f;
-    const int mode = m16_mode(q_norm_bound, k_norm_bound, sl, prescaled != 0);
-    if (use_xattn_persistent(true, 1, mode, cdiv(Lk, kKBlk)))
-      return mode == 1 ? "attn_fwd_m16<cross, prescaled, zero shift, persistent>"
-                       : (prescaled ? "attn_fwd_m16<cross, prescaled, online max, persistent>"
-                                    : "attn_fwd_m16<cross, online max, persistent>");
-  }
-  if (Lk > 4096 && prescaled) {
-    const int mode = m16_mode(q_norm_bound, k_norm_bound, 1.f, true, true);
-    const int rows = wide_rows(true, fp8, false, Lk, mode);  // (a gated pair returned above)
-    static const char* wq[2][2] = {
-        {"attn_fwd_wq<self, prescaled, 320 rows, fixed shift>", "attn_fwd_wq<self, prescaled, 320 rows, zero shift>"},
-        {"attn_fwd_wq<self, prescaled, 384 rows, fixed shift>", "attn_fwd_wq<self, prescaled, 384 rows, zero shift>"}};
-    if (rows) return wq[rows == 384][mode];
-  }
-  static const char* names[2][2][3] = {
-      {{"attn_fwd_m16<self, fixed shift>", "?", "attn_fwd_m16<self, online max>"},
-       {"attn_fwd_m16<self, prescaled, fixed shift>", "attn_fwd_m16<self, prescaled, zero shift>",
-        "attn_fwd_m16<self, prescaled, online max>"}},
-      {{"attn_fwd_m16<cross, fixed shift>", "?", "attn_fwd_m16<cross, online max>"},
-       {"attn_fwd_m16<cross, prescaled, fixed shift>", "attn_fwd_m16<cross, prescaled, zero shift>",
-        "attn_fwd_m16<cross, prescaled, online max>"}}};
-  const float sl = prescaled ? 1.f : softmax_scale * 1.4426950408889634f;
-  return names[Lk <= 4096][prescaled != 0][m16_mode(q_norm_bound, k_norm_bound, sl, prescaled != 0, Lk > 4096)];
+  return attn_route_name(attn_route(route_query(Lk, prescaled != 0, softmax_scale, q_norm_bound, k_norm_bound, fp8,
+                                                prescaled == 2, false, 1)));
 }

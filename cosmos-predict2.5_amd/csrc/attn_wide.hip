@@ -541,8 +541,8 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
 
 }  // namespace
 
-// Built: 320 and 384 rows, fixed shift. Every long-key launch with usable norm bounds is in the fixed mode (m16_mode's
-// whole_ok, round 6), so the zero-shift form (kMode 1: the same stream without the initial C) has no launch to serve
+// Built: 320 and 384 rows, fixed shift. Every long-key launch with usable norm bounds is in the fixed mode (attn_route's
+// long-key rule, round 6), so the zero-shift form (kMode 1: the same stream without the initial C) has no launch to serve
 // and is not instantiated.
 AttnKernel wq_kernel(int rows, int mode, bool tail) {
   if (mode != 0) return nullptr;

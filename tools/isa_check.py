@@ -18,9 +18,11 @@ _ASM_CACHE = {}
 
 
 def compile_asm(src, out=None, extra=()):
-    """(asm text, resource remarks per kernel) of src; cached per (source path, mtime, extra flags) in this process,
-    so several checks of one source compile it once."""
-    key = (os.path.abspath(src), os.path.getmtime(src), tuple(extra))
+    """(asm text, resource remarks per kernel) of src; cached per (source path, mtime of it and of the headers beside
+    it, extra flags) in this process, so several checks of one source compile it once."""
+    d = os.path.dirname(os.path.abspath(src))
+    deps = [src] + sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith(".h"))  # cp25_common.h, attn_*.h
+    key = (os.path.abspath(src), tuple(os.path.getmtime(f) for f in deps), tuple(extra))
     if key not in _ASM_CACHE:
         _ASM_CACHE[key] = _compile_asm(src, out or f"/tmp/isa_check_{os.getpid()}_{os.path.basename(src)}.s", extra)
     return _ASM_CACHE[key]
