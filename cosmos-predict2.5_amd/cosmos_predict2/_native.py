@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -111,6 +111,13 @@ SIGNATURES = {
     "cp25_gemm_hnorm": [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _P, _F, _F, _P],
     "cp25_gemm_qkv": [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P],
     "cp25_gemm_res": [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _P, _I64, _I64, _P, _I64, _I64, _I, _I64, _I64, _P],
+    "cp25_gemm_sm_epi": [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _I, _I, _P, _I64, _P],
+    "cp25_gemm_sm_res": [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _P, _I64, _I64, _P, _I64, _I64, _I, _I64, _I64, _I, _P,
+                         _I64, _P],
+    "cp25_gemm_sm_hnorm": [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _P, _F, _F, _I, _P, _I64, _P],
+    "cp25_gemm_sm_qkv": [_P, _I64, _P, _I64, _P, _I64, _I, _I, _I, _I, _I, _P, _P, _P, _I, _F, _I, _P, _I64, _P],
+    "cp25_gemm_sm_plan": [_I, _I, _I, _I, _I],
+    "cp25_gemm_sm_workspace_bytes": [_I, _I, _I, _I],
     "cp25_gemm_fp8": [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I, _I, _I, _P],
     "cp25_gemm_fp8_res": [_P, _I64, _P, _P, _I64, _P, _P, _I64, _I, _I, _I, _P, _I64, _I64, _P, _I64, _I64, _I, _I64,
                           _I64, _P],
@@ -172,6 +179,7 @@ def load_library() -> ctypes.CDLL:
             fn.argtypes = argtypes
         fn.restype = {"cp25_attn_workspace_bytes": ctypes.c_size_t, "cp25_attn_tail_workspace_bytes": ctypes.c_size_t, "cp25_v_fp8t_bytes": ctypes.c_int64,
                       "cp25_gemm_f32_workspace_floats": ctypes.c_int64,
+                      "cp25_gemm_sm_workspace_bytes": ctypes.c_int64,
                       "cp25_attn_kernel": ctypes.c_char_p,
                       "cp25_vae_attn_workspace_bytes": ctypes.c_int64}.get(name, ctypes.c_int)
     _lib = lib
@@ -839,6 +847,169 @@ def gemm_res(a: torch.Tensor, w: torch.Tensor, x: torch.Tensor, x_st: int, x_sb:
     rc = lib.cp25_gemm_res(_ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(out), out.stride(0), M, N, K, _ptr(x), x_st,
                            x_sb, _ptr(gate), gate.stride(0), gate.stride(1), B, tok0, hw, _stream(a.device))
     _check("cp25_gemm_res", rc)
+    return out
+
+
+# ---------------------------------------------------------------- small-M block GEMMs (csrc/gemm_small.hip)
+class GemmSmPlan(NamedTuple):
+    """cp25_gemm_sm_plan unpacked: small (the small family runs the shape), split (S >= 1), the output tile."""
+    small: bool
+    split: int
+    bm: int
+    bn: int
+
+
+def gemm_sm_plan(M: int, N: int, K: int, epilogue: int = 0, cus: int = 0) -> GemmSmPlan:
+    """The plan of a small-M launch (cp25_gemm_sm_plan; csrc/gemm_route.h). cus = 0: the current device's CU count (256
+    without a device)."""
+    v = load_library().cp25_gemm_sm_plan(int(M), int(N), int(K), int(epilogue), int(cus))
+    _check("cp25_gemm_sm_plan", min(v, 0))
+    return GemmSmPlan(bool(v & 1), (v >> 8) & 0xFF, ((v >> 16) & 0xFF) * 16, ((v >> 24) & 0x7F) * 16)
+
+
+def gemm_sm_workspace_bytes(M: int, N: int, K: int, split: int) -> int:
+    """Bytes of fp32 partial sums a small-M launch with this split needs (cp25_gemm_sm_workspace_bytes): 0 for split 1."""
+    return int(load_library().cp25_gemm_sm_workspace_bytes(int(M), int(N), int(K), int(split)))
+
+
+_SM_WS: Dict[torch.device, torch.Tensor] = {}
+
+
+def _sm_workspace(name: str, device: torch.device, M: int, N: int, K: int, epilogue: int, split: int, workspace):
+    """(S, workspace tensor or None, its bytes) of a small-M launch: split = 0 takes the plan's S; the workspace given,
+    or one buffer per device that grows to the largest launch and is reused (launches on one stream are ordered; a
+    caller running small-M GEMMs on several streams at once passes its own)."""
+    split = int(split)
+    if split < 0:
+        raise ValueError(f"{name}: split must be >= 0, got {split}")
+    if N % 256 or K % 64:
+        raise ValueError(f"{name}: needs N % 256 == 0 and K % 64 == 0, got N = {N}, K = {K}")
+    S = split if split else gemm_sm_plan(M, N, K, epilogue).split
+    if S > K // 64:
+        raise ValueError(f"{name}: split {S} exceeds the {K // 64} K-tiles of K = {K}")
+    need = gemm_sm_workspace_bytes(M, N, K, S)
+    if workspace is not None:
+        if not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != device:
+            raise ValueError(f"{name}: the workspace must be a contiguous tensor on {device}")
+        return S, workspace, workspace.numel() * workspace.element_size()
+    if not need:
+        return S, None, 0
+    ws = _SM_WS.get(device)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(need, dtype=torch.uint8, device=device)
+        _SM_WS[device] = ws
+    return S, ws, ws.numel()
+
+
+def gemm_sm_epi(a: torch.Tensor, w: torch.Tensor, epilogue: int = EPI_NONE, out: Optional[torch.Tensor] = None, *,
+                split: int = 0, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemm_epi on the small-M family (cp25_gemm_sm_epi): split = 1 the exact one-pass form, bit-identical to gemm_epi;
+    split = S > 1 the split-K form (fixed addition order, bits depend on S only); split = 0 the plan's S. workspace:
+    None (a per-device buffer, allocated and reused) or the caller's; too small a one is a ValueError."""
+    lib = load_library()
+    if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise ValueError("gemm_sm_epi expects bf16 operands")
+    if a.dim() != 2 or w.dim() != 2 or a.shape[1] != w.shape[1] or a.stride(1) != 1 or w.stride(1) != 1:
+        raise ValueError(f"gemm_sm_epi shapes a{tuple(a.shape)} w{tuple(w.shape)}: need [M, K] x [N, K], K contiguous")
+    M, K = a.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"gemm_sm_epi out {tuple(out.shape)} != ({M}, {N})")
+    S, ws, nws = _sm_workspace("gemm_sm_epi", a.device, M, N, K, int(epilogue), split, workspace)
+    rc = lib.cp25_gemm_sm_epi(_ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(out), out.stride(0), M, N, K,
+                              int(epilogue), S, _ptr(ws), nws, _stream(a.device))
+    _check("cp25_gemm_sm_epi", rc)
+    return out
+
+
+def gemm_sm_hnorm(a: torch.Tensor, w: torch.Tensor, norm_weight: torch.Tensor, *, out_scale: float = 1.0,
+                  eps: float = 1e-6, out: Optional[torch.Tensor] = None, split: int = 0,
+                  workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemm_hnorm on the small-M family (cp25_gemm_sm_hnorm; split / workspace as gemm_sm_epi). Built for either parity
+    of K / 64, so it never returns None."""
+    lib = load_library()
+    if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or norm_weight.dtype != torch.bfloat16:
+        raise ValueError("gemm_sm_hnorm expects bf16 operands and norm weight")
+    if a.dim() != 2 or w.dim() != 2 or a.shape[1] != w.shape[1] or a.stride(1) != 1 or w.stride(1) != 1:
+        raise ValueError(f"gemm_sm_hnorm shapes a{tuple(a.shape)} w{tuple(w.shape)}: need [M, K] x [N, K], K contiguous")
+    if norm_weight.numel() != 128 or not norm_weight.is_contiguous() or norm_weight.device != a.device:
+        raise ValueError("gemm_sm_hnorm: norm_weight must be a contiguous bf16 [128] device tensor")
+    M, K = a.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"gemm_sm_hnorm out {tuple(out.shape)} != ({M}, {N})")
+    S, ws, nws = _sm_workspace("gemm_sm_hnorm", a.device, M, N, K, EPI_HNORM, split, workspace)
+    rc = lib.cp25_gemm_sm_hnorm(_ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(out), out.stride(0), M, N, K,
+                                _ptr(norm_weight), float(eps), float(out_scale), S, _ptr(ws), nws, _stream(a.device))
+    _check("cp25_gemm_sm_hnorm", rc)
+    return out
+
+
+def gemm_sm_qkv(a: torch.Tensor, w: torch.Tensor, k_norm_weight: torch.Tensor, *, k_col0: int, k_cols: int, B: int,
+                cos: Optional[torch.Tensor] = None, sin: Optional[torch.Tensor] = None, eps: float = 1e-6,
+                out: Optional[torch.Tensor] = None, split: int = 0,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemm_qkv on the small-M family (cp25_gemm_sm_qkv; split / workspace as gemm_sm_epi). Built for either parity of
+    K / 64, so it never returns None."""
+    lib = load_library()
+    if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or k_norm_weight.dtype != torch.bfloat16:
+        raise ValueError("gemm_sm_qkv expects bf16 operands and norm weight")
+    if a.dim() != 2 or w.dim() != 2 or a.shape[1] != w.shape[1] or a.stride(1) != 1 or w.stride(1) != 1:
+        raise ValueError(f"gemm_sm_qkv shapes a{tuple(a.shape)} w{tuple(w.shape)}: need [M, K] x [N, K], K contiguous")
+    if k_norm_weight.numel() != 128 or not k_norm_weight.is_contiguous() or k_norm_weight.device != a.device:
+        raise ValueError("gemm_sm_qkv: k_norm_weight must be a contiguous bf16 [128] device tensor")
+    M, K = a.shape
+    N = w.shape[0]
+    if (cos is None) != (sin is None):
+        raise ValueError("gemm_sm_qkv: cos and sin go together")
+    if cos is not None:
+        for t in (cos, sin):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 2 or t.shape[1] != 64 or \
+                    t.shape[0] * B < M or t.device != a.device:
+                raise ValueError(f"gemm_sm_qkv: cos/sin must be contiguous float32 [>= {M // B}, 64] device tables")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"gemm_sm_qkv out {tuple(out.shape)} != ({M}, {N})")
+    S, ws, nws = _sm_workspace("gemm_sm_qkv", a.device, M, N, K, EPI_QKV, split, workspace)
+    rc = lib.cp25_gemm_sm_qkv(_ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(out), out.stride(0), M, N, K, int(k_col0),
+                              int(k_cols), _ptr(k_norm_weight), _ptr(cos), _ptr(sin), int(B), float(eps), S, _ptr(ws),
+                              nws, _stream(a.device))
+    _check("cp25_gemm_sm_qkv", rc)
+    return out
+
+
+def gemm_sm_res(a: torch.Tensor, w: torch.Tensor, x: torch.Tensor, x_st: int, x_sb: int, gate: torch.Tensor, *, B: int,
+                tok0: int, hw: int, out: Optional[torch.Tensor] = None, split: int = 0,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemm_res on the small-M family (cp25_gemm_sm_res; split / workspace as gemm_sm_epi)."""
+    lib = load_library()
+    if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or gate.dtype != torch.bfloat16:
+        raise ValueError("gemm_sm_res expects bf16 operands")
+    if a.dim() != 2 or w.dim() != 2 or a.shape[1] != w.shape[1] or a.stride(1) != 1 or w.stride(1) != 1:
+        raise ValueError(f"gemm_sm_res shapes a{tuple(a.shape)} w{tuple(w.shape)}: need [M, K] x [N, K], K contiguous")
+    M, K = a.shape
+    N = w.shape[0]
+    if gate.dim() != 3 or gate.shape[-1] != N or gate.stride(2) != 1 or gate.shape[0] < B:
+        raise ValueError(f"gemm_sm_res gate {tuple(gate.shape)}: need a [B, T, {N}] view with a unit inner stride")
+    n_tok = M // B
+    _check_frames(gate, n_tok=n_tok, B=B, tok0=tok0, hw=hw)
+    if M % B or x.stride(-1) != 1 or \
+            (n_tok - 1) * x_st + (B - 1) * x_sb + N > x.untyped_storage().nbytes() // 2 - x.storage_offset():
+        raise ValueError("gemm_sm_res: x does not cover the rows")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+    if tuple(out.shape) != (M, N) or out.stride(1) != 1:
+        raise ValueError(f"gemm_sm_res out {tuple(out.shape)} != ({M}, {N})")
+    S, ws, nws = _sm_workspace("gemm_sm_res", a.device, M, N, K, EPI_RES, split, workspace)
+    rc = lib.cp25_gemm_sm_res(_ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(out), out.stride(0), M, N, K, _ptr(x),
+                              x_st, x_sb, _ptr(gate), gate.stride(0), gate.stride(1), B, tok0, hw, S, _ptr(ws), nws,
+                              _stream(a.device))
+    _check("cp25_gemm_sm_res", rc)
     return out
 
 

@@ -73,6 +73,10 @@ class SetupArguments(pydantic.BaseModel):
     # build-specific, like state_t (the reference has no such field): "host" resizes, normalises and quantises pixels
     # with torch on the CPU / in fp32; "device" keeps them uint8 on the GPU (cosmos_predict2/pixels.py)
     pixel_path: Literal["host", "device"] = "host"
+    # build-specific: the GEMM family of the streaming student's per-frame forward (MinimalV1LVGDiT.stream_gemm):
+    # "tile256" (default) the 256 x 256-tile kernels, "small" the small-M kernels' exact form (the same bits),
+    # "small_splitk" their planned K split. Read by forward_frame only; bf16 linears only
+    stream_gemm: Literal["tile256", "small", "small_splitk"] = "tile256"
     # LoRA post-training (the reference's use_lora / lora_rank / lora_alpha recipe): an adapter-only file (safetensors or
     # .pt) merged into the checkpoint's weights at load; lora_alpha None means alpha = the adapter's rank (32 / 32 in
     # the shipped recipe). alpha and scale also apply to a checkpoint_path that is itself in peft's layout

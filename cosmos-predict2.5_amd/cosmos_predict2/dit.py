@@ -344,6 +344,16 @@ class MinimalV1LVGDiT:
         # the Q fragments as they load, bit-identical, no separate pass over q in HBM); prescaled bf16 form only
         self.fused_q_norm = True
         self._x_embed_w128 = None  # the x_embedder weight zero-padded to K = 128 (embed_patches' own-GEMM path)
+        # forward_frame's block GEMMs (read by forward_frame only; forward_tokens ignores it): "tile256" (default) the
+        # 256 x 256-tile cp25_gemm_*; "small" the small-M family's exact form (cp25_gemm_sm_*, split 1) wherever its plan
+        # (cp25_gemm_sm_plan) takes the shape: the same bits; "small_splitk" the plan's K split (fixed addition order:
+        # the same bits run to run, not the bits of "tile256"). bf16 linears only. See set_stream_gemm.
+        self.stream_gemm = "tile256"
+        # test hook: overrides the plan's S under "small_splitk" (clamped to K / 64), e.g. 2 on a tiny net whose K = 512
+        # the plan would not split
+        self.stream_gemm_force_split: Optional[int] = None
+        self._sg: Optional[str] = None  # the mode in force inside a forward_frame call, None outside / "tile256"
+        self._sg_plans: Dict[Tuple[int, int, int, int], "N.GemmSmPlan"] = {}
         # sparse blocks (cfg.n_dense_blocks / natten_parameters): per-block NattenParams, None = dense; their
         # neighborhood plans (sparse_attn.build_plan) are cached per (patch grid, parameters)
         self.sparse_params = sparse_block_params(cfg.num_blocks, cfg.n_dense_blocks, cfg.natten_parameters or None)
@@ -380,6 +390,44 @@ class MinimalV1LVGDiT:
             raise ValueError(f"linear precision must be 'bf16' or 'fp8', got {precision!r}")
         self.linear_precision = precision
         self._fp8_w = {}
+
+    STREAM_GEMM_MODES = ("tile256", "small", "small_splitk")
+
+    def _check_stream_gemm(self) -> None:
+        if self.stream_gemm not in self.STREAM_GEMM_MODES:
+            raise ValueError(f"stream_gemm must be one of {self.STREAM_GEMM_MODES}, got {self.stream_gemm!r}")
+        if self.stream_gemm != "tile256" and self.linear_precision == "fp8":
+            raise ValueError(f"stream_gemm={self.stream_gemm!r} with linear_precision='fp8': the small-M GEMMs are bf16 "
+                             "only (a small-M fp8 form is not built)")
+        fs = self.stream_gemm_force_split
+        if fs is not None and (not isinstance(fs, int) or fs < 1):
+            raise ValueError(f"stream_gemm_force_split must be None or an int >= 1, got {fs!r}")
+
+    def set_stream_gemm(self, mode: str) -> None:
+        """Which GEMM family forward_frame's block projections run on (the stream_gemm attribute, checked here and again
+        by every forward_frame): "tile256", "small" or "small_splitk". ValueError for another value, or for a value
+        other than "tile256" under linear_precision "fp8"."""
+        old, self.stream_gemm = self.stream_gemm, mode
+        try:
+            self._check_stream_gemm()
+        except ValueError:
+            self.stream_gemm = old
+            raise
+
+    def _sm_split(self, M: int, w: torch.Tensor, epilogue: int) -> Optional[int]:
+        """The split with which this [M, K] x [N, K] projection runs on the small-M family, or None: cp25_gemm_* (outside
+        forward_frame, under "tile256", or where the plan leaves the shape to the 256 x 256 tiles)."""
+        if self._sg is None:
+            return None
+        key = (M, w.shape[0], w.shape[1], epilogue)
+        plan = self._sg_plans.get(key)
+        if plan is None:
+            plan = self._sg_plans[key] = N.gemm_sm_plan(*key)
+        if not plan.small:
+            return None
+        if self._sg == "small":
+            return 1
+        return min(self.stream_gemm_force_split or plan.split, w.shape[1] // 64)
 
     def set_attention_precision(self, precision: str) -> None:
         """"bf16" (default, the reference's arithmetic), "fp8qk" or "fp8" (config 5's option; no reference
@@ -496,6 +544,9 @@ class MinimalV1LVGDiT:
         D, H = cfg.model_channels, cfg.num_heads
         x, w, kw = _rows(h, n_rows), self.w_qkv[i], self.sd[f"blocks.{i}.self_attn.k_norm.weight"]
         if kslots is None and self._own(x, w):
+            S = self._sm_split(n_rows, w, N.EPI_QKV)
+            if S is not None:
+                return N.gemm_sm_qkv(x, w, kw, k_col0=D, k_cols=D, B=B, cos=cos, sin=sin, split=S)
             qkv = N.gemm_qkv(x, w, kw, k_col0=D, k_cols=D, B=B, cos=cos, sin=sin)
             if qkv is not None:
                 return qkv
@@ -517,7 +568,11 @@ class MinimalV1LVGDiT:
         fused = None
         path = self._fused_res(a, w, B, geo.hw)
         if path == 1:
-            fused = N.gemm_res(a, w, x, x_st, x_sb, gate, B=B, tok0=geo.tok0, hw=geo.hw)
+            S = self._sm_split(a.shape[0], w, N.EPI_RES)
+            if S is not None:
+                fused = N.gemm_sm_res(a, w, x, x_st, x_sb, gate, B=B, tok0=geo.tok0, hw=geo.hw, split=S)
+            else:
+                fused = N.gemm_res(a, w, x, x_st, x_sb, gate, B=B, tok0=geo.tok0, hw=geo.hw)
         elif path == 2:
             q, s = a if isinstance(a, tuple) else N.quant_fp8_rows(a, gelu=gelu_in)
             w8, ws = self._fp8_weight(key, w)
@@ -1098,6 +1153,9 @@ class MinimalV1LVGDiT:
                 wp = torch.zeros((D, 128), dtype=BF16, device=self.device)
                 wp[:, :f] = w[:, :f]
                 self._x_embed_w128 = wp
+            S = self._sm_split(a.shape[0], wp, N.EPI_NONE)
+            if S is not None:
+                return N.gemm_sm_epi(a, wp, split=S).view(n, Bx, D)
             return N.gemm_epi(a, wp).view(n, Bx, D)
         V = geo.n_views
         if view_indices is None:
@@ -1138,6 +1196,9 @@ class MinimalV1LVGDiT:
         camera (prepare_camera; camera-conditioned nets): every block's self-attention reads
         bf16(h + cam_emb_i[token]) (camera/networks/minimal_v4_dit_camera_conditioned.py:1189-1194), the same camera in
         every batch entry, so the shared block-0 prefix stays valid. Single GPU only.
+
+        The stream_gemm option (the small-M GEMM family) is forward_frame's alone: forward_tokens ignores it and runs
+        cp25_gemm_* whatever its value.
 
         CP = 1: one pass over the batch (B = 2 = [cond, uncond]).
         CP > 1: the batch entries run as two software-pipelined lanes on the current stream: each
@@ -1253,8 +1314,12 @@ class MinimalV1LVGDiT:
         see up to rounding. The slot is written on every pass: a denoising pass (store=False) leaves its noisy K / V
         there, no later frame reads them before the store pass (store=True, on the clean frame) overwrites them, and
         the slot is none of the history's. store=True also marks the frame as stored: frames are stored in order, and
-        frame t runs only once frames 0 .. t - 1 are."""
+        frame t runs only once frames 0 .. t - 1 are.
+        The block GEMMs (fused QKV, the output / cross-output / MLP layer 2 projections with their residuals, the
+        cross-attention q projection, MLP layer 1) and the patch embedder run on the family `stream_gemm` names (see
+        __init__): "tile256" by default."""
         cfg = self.cfg
+        self._check_stream_gemm()
         if cfg.camera_dim:
             raise ValueError("a camera-conditioned net combined with forward_frame (the K/V cache) is not built")
         if cfg.use_wan_fp32_strategy or cfg.n_cameras_emb or cfg.cross_view_attn_map:
@@ -1278,24 +1343,28 @@ class MinimalV1LVGDiT:
         if tuple(t_B_1.shape) != (B, 1) or patch_rows.shape[0] != hw:
             raise ValueError(f"forward_frame takes t [B, 1] and one frame's {hw} patch rows")
         one = Geometry(T=1, Hp=geo.Hp, Wp=geo.Wp, tok0=0, n_tok=hw)
-        x_in = self.embed_patches(patch_rows, one, rows_k128=rows_k128)
-        emb = False
-        if action is not None:
-            if not cfg.action_dim:
-                raise ValueError("`action` given to a net without action embedders")
-            emb = self.frame_action_embedding(action, B)
-        mods, shift_f, scale_f = self._time_modulation_bf16(t_B_1.to(self.device), action_emb=emb)
-        full = Geometry(T=geo.T, Hp=geo.Hp, Wp=geo.Wp, tok0=frame_idx * hw, n_tok=hw)
-        cos, sin = self.rope_tables(full)
-        kv = (cache, cache.slot(frame_idx), cache.n_valid(frame_idx))
-        gen = self._blocks(x_in, mods, shift_f, scale_f, ctx, one, cos, sin, None, 1, kv=kv)
-        while True:
-            try:
-                next(gen)
-            except StopIteration as e:
-                if store:
-                    cache.n_stored = frame_idx + 1
-                return e.value
+        self._sg = None if self.stream_gemm == "tile256" else self.stream_gemm
+        try:
+            x_in = self.embed_patches(patch_rows, one, rows_k128=rows_k128)
+            emb = False
+            if action is not None:
+                if not cfg.action_dim:
+                    raise ValueError("`action` given to a net without action embedders")
+                emb = self.frame_action_embedding(action, B)
+            mods, shift_f, scale_f = self._time_modulation_bf16(t_B_1.to(self.device), action_emb=emb)
+            full = Geometry(T=geo.T, Hp=geo.Hp, Wp=geo.Wp, tok0=frame_idx * hw, n_tok=hw)
+            cos, sin = self.rope_tables(full)
+            kv = (cache, cache.slot(frame_idx), cache.n_valid(frame_idx))
+            gen = self._blocks(x_in, mods, shift_f, scale_f, ctx, one, cos, sin, None, 1, kv=kv)
+            while True:
+                try:
+                    next(gen)
+                except StopIteration as e:
+                    if store:
+                        cache.n_stored = frame_idx + 1
+                    return e.value
+        finally:
+            self._sg = None
 
     def _view_modulation(self, mods: torch.Tensor, geo: Geometry, view_indices: Optional[torch.Tensor]) -> torch.Tensor:
         """Cross-view nets' AdaLN view embedding (multiview_cross_dit.py:807-813, 355-404): adaln_view_proj(
@@ -1520,7 +1589,11 @@ class MinimalV1LVGDiT:
             hq, wq = _rows(h, n * Bs), p[pre + "cross_attn.q_proj.weight"]
             qc = None
             if self._own(hq, wq):  # the q RMSNorm (+ prescale) in the GEMM's epilogue (cp25_gemm_hnorm, bit-identical)
-                qc = N.gemm_hnorm(hq, wq, p[pre + "cross_attn.q_norm.weight"], out_scale=xq_scale)
+                S = self._sm_split(hq.shape[0], wq, N.EPI_HNORM)
+                if S is not None:
+                    qc = N.gemm_sm_hnorm(hq, wq, p[pre + "cross_attn.q_norm.weight"], out_scale=xq_scale, split=S)
+                else:
+                    qc = N.gemm_hnorm(hq, wq, p[pre + "cross_attn.q_norm.weight"], out_scale=xq_scale)
             if qc is None:
                 qc = self._proj(hq, wq, pre + "cross_attn.q_proj")
                 N.head_rmsnorm_rope(qc, n_rows=n * Bs, B=Bs, H=H, head_off=0,
@@ -1542,7 +1615,11 @@ class MinimalV1LVGDiT:
             if self._own(h1, w1):
                 # layer1 + exact-erf GELU in one hand-written MFMA GEMM (the epilogue applies it to the bf16 product, as
                 # cp25_gelu would): the [n B, 4 D] hidden makes one HBM trip instead of three
-                u = N.gemm_epi(h1, w1, epilogue=N.EPI_GELU)
+                S = self._sm_split(h1.shape[0], w1, N.EPI_GELU)
+                if S is not None:
+                    u = N.gemm_sm_epi(h1, w1, epilogue=N.EPI_GELU, split=S)
+                else:
+                    u = N.gemm_epi(h1, w1, epilogue=N.EPI_GELU)
             else:  # fp8 option: the GELU rides in layer2's row quantisation
                 u = self._linear(h1, w1, pre + "mlp.layer1")
             if self._fused_res(u, w2, B, geo.hw):

@@ -37,7 +37,8 @@ class Inference:
                                          context_parallel_size=args.context_parallel_size or 1,
                                          state_t=args.state_t, text_encoder=text_encoder,
                                          pixel_path=args.pixel_path, lora_path=args.lora_path,
-                                         lora_alpha=args.lora_alpha, lora_scale=args.lora_scale)
+                                         lora_alpha=args.lora_alpha, lora_scale=args.lora_scale,
+                                         stream_gemm=args.stream_gemm)
         if self.rank0:
             Path(args.output_dir).mkdir(parents=True, exist_ok=True)
 

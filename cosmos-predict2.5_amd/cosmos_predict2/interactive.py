@@ -30,11 +30,16 @@ class ActionStreamingInference:
     """`generate_action_streaming` (the whole video) and `stream_action_chunks` (a generator: each chunk's frames as soon
     as they are decoded) over one pipeline object (the tokenizer and the streaming student)."""
 
-    def __init__(self, text_embeddings: torch.Tensor, pipe: Optional[Video2WorldInference] = None, **pipe_kwargs):
+    def __init__(self, text_embeddings: torch.Tensor, pipe: Optional[Video2WorldInference] = None,
+                 stream_gemm: Optional[str] = None, **pipe_kwargs):
         """text_embeddings: [Lctx, dim] or [1, Lctx, dim], what the net's text context takes (the empty-string
         embedding in the reference). pipe_kwargs go to Video2WorldInference (ckpt_path, tokenizer_path, pixel_path,
-        lora_path / lora_alpha / lora_scale for a LoRA post-trained student, net_cfg / sampler_cfg overrides, ...)."""
+        lora_path / lora_alpha / lora_scale for a LoRA post-trained student, net_cfg / sampler_cfg overrides, ...).
+        stream_gemm: "tile256" (the default of a pipeline made here), "small" or "small_splitk": the GEMM family of the
+        per-frame forward (Video2WorldInference(stream_gemm=...)); None leaves a given `pipe` as it is."""
         self.pipe = pipe or Video2WorldInference(MODEL_NAME, **pipe_kwargs)
+        if stream_gemm is not None:
+            self.pipe.model.net.set_stream_gemm(stream_gemm)
         if self.pipe.model.config.sampler != "dmd2_stream":
             raise ValueError("ActionStreamingInference needs a streaming ('dmd2_stream') model")
         emb = text_embeddings

@@ -111,7 +111,7 @@ class Video2WorldInference:
                  net_cfg: Optional[DiTConfig] = None, sampler_cfg: Optional[SamplerConfig] = None,
                  weights_seed: int = 0, linear_precision: str = "bf16", attention_precision: str = "bf16",
                  pixel_path: str = "host", lora_path: Optional[str] = None, lora_alpha: Optional[float] = None,
-                 lora_scale: float = 1.0):
+                 lora_scale: float = 1.0, stream_gemm: str = "tile256"):
         """linear_precision: "bf16" (the reference's arithmetic) or "fp8" (the DiT block GEMMs as fp8
         MFMA, config 5's option; MinimalV1LVGDiT.set_linear_precision). attention_precision: "bf16", "fp8qk"
         (self-attention Q K^T on e4m3) or "fp8" (also P.V; MinimalV1LVGDiT.set_attention_precision).
@@ -120,7 +120,10 @@ class Video2WorldInference:
         lora_path: an adapter-only LoRA file (safetensors or .pt: lora_A / lora_B tensors) merged into the loaded
         weights once, on the device (MinimalV1LVGDiT.merge_lora); lora_alpha (None: the adapter's rank, the recipe's
         32 / 32) and lora_scale (1.0) set its strength, scale = lora_scale * alpha / r. They apply as well to a
-        ckpt_path that is itself in peft's layout (base_layer. keys plus adapters), which needs no lora_path."""
+        ckpt_path that is itself in peft's layout (base_layer. keys plus adapters), which needs no lora_path.
+        stream_gemm: the GEMM family of the streaming student's per-frame forward (MinimalV1LVGDiT.stream_gemm):
+        "tile256" (default), "small" (the small-M kernels' exact form: the same bits) or "small_splitk" (their planned
+        K split); bf16 linears only."""
         if pixel_path not in ("host", "device"):
             raise ValueError(f"pixel_path must be 'host' or 'device', got {pixel_path!r}")
         self.pixel_path = pixel_path
@@ -161,6 +164,7 @@ class Video2WorldInference:
         self.model.pixel_path = pixel_path
         self.model.net.set_linear_precision(linear_precision)
         self.model.net.set_attention_precision(attention_precision)
+        self.model.net.set_stream_gemm(stream_gemm)
         if self.process_group is not None:
             self.model.set_context_parallel_group(self.process_group)
         emb_dim = ncfg.crossattn_proj_in_channels if ncfg.use_crossattn_projection else ncfg.crossattn_emb_channels

@@ -89,6 +89,25 @@ __device__ __forceinline__ float gelu_erf(float x) {
   return x * (x >= 0.f ? fmaf(-0.5f, ec, 1.f) : 0.5f * ec);
 }
 
+// x + gate * y on 8 bf16 columns, two bf16 roundings (the reference's two torch ops, = cp25_ln_mod's residual)
+__device__ __forceinline__ u32x4 res8(u32x4 y, u32x4 x, u32x4 g) {
+#pragma clang fp contract(off)
+  u32x4 o;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    unsigned r = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const float yv = bf2f((unsigned short)(y[w] >> (16 * h)));
+      const float xv = bf2f((unsigned short)(x[w] >> (16 * h)));
+      const float gv = bf2f((unsigned short)(g[w] >> (16 * h)));
+      r |= (unsigned)f2bf(rbf(xv + rbf(gv * yv))) << (16 * h);
+    }
+    o[w] = r;
+  }
+  return o;
+}
+
 __host__ __device__ __forceinline__ int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // XCD-aware bijective remap of a 1-D grid: blocks b and b+8 share an XCD, so give each

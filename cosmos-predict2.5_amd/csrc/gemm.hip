@@ -84,23 +84,7 @@ struct ResEpi {
   const float* rcos; const float* rsin; int n_lo, n_hi;
 };
 
-// x + gate * y on 8 bf16 columns, two bf16 roundings (the reference's two torch ops, = cp25_ln_mod's residual)
-__device__ __forceinline__ u32x4 res8(u32x4 y, u32x4 x, u32x4 g) {
-  u32x4 o;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    unsigned r = 0;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const float yv = bf2f((unsigned short)(y[w] >> (16 * h)));
-      const float xv = bf2f((unsigned short)(x[w] >> (16 * h)));
-      const float gv = bf2f((unsigned short)(g[w] >> (16 * h)));
-      r |= (unsigned)f2bf(rbf(xv + rbf(gv * yv))) << (16 * h);
-    }
-    o[w] = r;
-  }
-  return o;
-}
+// (res8, the two-rounding residual on 8 bf16 columns: cp25_common.h, shared with gemm_small.hip)
 
 template <int kEpi>
 __global__ void __launch_bounds__(kThreads, 1)

@@ -402,6 +402,46 @@ int cp25_gemm_res(const void* a, int64_t lda, const void* w, int64_t ldw, void* 
                   const void* x, int64_t x_st, int64_t x_sb, const void* gate, int64_t g_sb, int64_t g_st, int B,
                   int64_t tok0, int64_t hw, hipStream_t stream);
 
+/* ---------------------------------------------------------------- small-M block projections (streaming per-frame forward)
+ * The four entry points above for M from 1 to a few thousand rows, where their 256 x 256 tiles leave most CUs idle:
+ * 64 x 128 output tiles, one per workgroup (gemm_small.hip). Each takes its counterpart's arguments, with the same
+ * meanings and host checks, followed by (split, workspace, workspace_bytes). N % 256 == 0 and K % 64 == 0 (-95
+ * otherwise), any parity of K / 64 for every epilogue (CP25_EPI_HNORM and CP25_EPI_QKV included: unlike
+ * cp25_gemm_hnorm / _qkv these do not refuse odd K / 64).
+ *   split == 1: one pass, no workspace (workspace may be NULL). Every output element is the same MFMA chain as in
+ *     cp25_gemm_*: bit-identical to them on any data, for every epilogue.
+ *   split == S > 1: K is cut into S contiguous runs of whole 64-deep K-tiles (the first (K / 64) % S runs one tile
+ *     longer); each run accumulates in fp32 into workspace [S][M][N], a second kernel adds an element's S sums in
+ *     ascending run order in fp32, rounds once to bf16 and applies the epilogue once. Bits depend on S only: not on M,
+ *     the CU count or timing (no atomics). S <= K / 64 (-22 otherwise); workspace 16-B aligned with at least
+ *     cp25_gemm_sm_workspace_bytes(M, N, K, S) bytes (-22 otherwise, before any launch).
+ *   split == 0: the S of cp25_gemm_sm_plan for the current device.
+ * A row's result does not depend on M in either form.
+ * Replaces: the same nn.Linear layers as cp25_gemm_epi / _res / _hnorm / _qkv, as the causal student's per-frame
+ * forward runs them on one latent frame's rows (interactive/networks/dit_causal.py: CausalAttention's q/k/v/output
+ * projections, the cross-attention's q and output projections, GPT2FeedForward layer1 / layer2, and the PatchEmbed
+ * linear at K = 128). */
+int cp25_gemm_sm_epi(const void* a, int64_t lda, const void* w, int64_t ldw, void* c, int64_t ldc, int M, int N, int K,
+                     int epilogue, int split, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cp25_gemm_sm_res(const void* a, int64_t lda, const void* w, int64_t ldw, void* c, int64_t ldc, int M, int N, int K,
+                     const void* x, int64_t x_st, int64_t x_sb, const void* gate, int64_t g_sb, int64_t g_st, int B,
+                     int64_t tok0, int64_t hw, int split, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int cp25_gemm_sm_hnorm(const void* a, int64_t lda, const void* w, int64_t ldw, void* c, int64_t ldc, int M, int N, int K,
+                       const void* norm_weight, float eps, float out_scale, int split, void* workspace,
+                       int64_t workspace_bytes, hipStream_t stream);
+int cp25_gemm_sm_qkv(const void* a, int64_t lda, const void* w, int64_t ldw, void* c, int64_t ldc, int M, int N, int K,
+                     int k_col0, int k_cols, const void* k_norm_weight, const float* cos_tab, const float* sin_tab, int B,
+                     float eps, int split, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/* The plan of a small-M launch (gemm_route.h, a pure function of its arguments): bit 0 set when the small family runs
+ * this shape (clear: cp25_gemm_*'s 256 x 256 tiles measured faster, or the shape is outside the family's range),
+ * bits 8-15 the K split S (>= 1), bits 16-23 and 24-30 the output tile's rows / 16 and columns / 16; or a negative error
+ * code. cus: the CU count to plan for; 0: the current device's, or 256 without a device. */
+int cp25_gemm_sm_plan(int M, int N, int K, int epilogue, int cus);
+
+/* Bytes of workspace a small-M launch with this split needs: split * M * N * 4 for split > 1, else 0. */
+int64_t cp25_gemm_sm_workspace_bytes(int M, int N, int K, int split);
+
 /* The config-5 fp8 option's block projections on the same hand-written GEMM (no reference counterpart: the reference
  * has no fp8 path): C[M, N] = bf16((A[M, K] W[N, K]^T) * a_scale[m] * w_scale[n]) with A and W OCP e4m3 bytes
  * (row-scaled activations from cp25_ln_mod_fp8 / cp25_quant_fp8_rows / cp25_gelu_quant_fp8; per-output-channel weight

@@ -2,6 +2,7 @@
 """The streaming action student (2B/robot/action-cond/streaming) on one MI355X: time per latent frame and its anatomy.
 
     python tools/bench_streaming.py --resolution 256,320 [--num-steps 4] [--cache-frame-size -1] [--out DIR]
+                                    [--stream-gemm tile256|small|small_splitk]
 
 One process per run (one resolution). Seeded synthetic weights: the arithmetic, not the picture, is timed. It runs the
 chunk loop of ActionStreamingInference on one 13-frame chunk (T = 4 latent frames: the conditioning frame's prefill, then
@@ -15,6 +16,9 @@ three generated frames of num_steps evaluations + one store pass each) and repor
     (an unprofiled chunk's event-timed duration); the profiler stretches the host side, not the kernels;
   * the tile count of each block GEMM launch at this frame's row count against the CU count: every launch with fewer
     256 x 256 output tiles than CUs leaves CUs without work (the persistent GEMM runs one tile per workgroup round).
+--stream-gemm: the GEMM family of the per-frame forward (Video2WorldInference(stream_gemm=...)); the mode is written into
+the JSON line, with the spread of the timed chunks' latent-frame times (max - min) as the noise two modes are compared
+against.
 Prints one JSON line; with --out also appends it to <out>/streaming.jsonl.
 """
 from __future__ import annotations
@@ -71,12 +75,13 @@ def main():
     ap.add_argument("--num-steps", type=int, default=4)
     ap.add_argument("--cache-frame-size", type=int, default=-1)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--stream-gemm", default="tile256", choices=("tile256", "small", "small_splitk"))
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     h, w = (int(x) for x in a.resolution.split(","))
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
-    pipe = Video2WorldInference(MODEL_NAME, device=dev, pixel_path="device")
+    pipe = Video2WorldInference(MODEL_NAME, device=dev, pixel_path="device", stream_gemm=a.stream_gemm)
     model, ncfg = pipe.model, pipe.model.net_cfg
     rng = np.random.RandomState(0)
     frame = torch.from_numpy(rng.randint(0, 256, size=(3, h, w), dtype=np.uint8)).to(dev)
@@ -133,7 +138,9 @@ def main():
                                                                ("mlp1", ncfg.mlp_hidden))}
     res = dict(workload=f"streaming action student, one 13-frame chunk at {h}x{w} ({hw} tokens per latent frame), "
                         f"{a.num_steps} steps, cache_frame_size {a.cache_frame_size}, bf16, synthetic weights",
-               ms_per_latent_frame=float(np.median(per_frame)), ms_per_denoise_eval=float(np.median(denoise)),
+               stream_gemm=a.stream_gemm, ms_per_latent_frame=float(np.median(per_frame)),
+               ms_per_latent_frame_all=per_frame, ms_per_latent_frame_spread=float(max(per_frame) - min(per_frame)),
+               ms_per_denoise_eval=float(np.median(denoise)),
                ms_per_store_eval=float(np.median(store)), chunk_ms_best=best["chunk_ms"],
                chunk_ms_all=[c["chunk_ms"] for c in chunks], frames_per_s_dit=12e3 / best["chunk_ms"],
                vae_encode_ms=enc_ms, vae_decode_ms=dec_ms,
