@@ -150,6 +150,12 @@ SIGNATURES = {
     "cp25_u8_to_clip": [_P, c_int64_p, _I, _I, _I, _I, _P, _P],
     "cp25_clip_to_u8": [_P, c_int64_p, _I, _I, _I, _I, _P, c_int64_p, _P],
     "cp25_lora_merge": [_P, _I64, _P, _P, _I64, _I64, _I, _F, _P],
+    "cp25_embed_gather": [_P, _I64, _I64, _P, _P, _I64, _I64, _P],
+    "cp25_add_rmsnorm": [_P, _I64, _P, _I64, _P, _P, _I64, _I64, _I64, _F, _P],
+    "cp25_rope_qk": [_P, _I64, _I64, _I, _I, _P, _P, _P],
+    "cp25_swiglu": [_P, _I64, _P, _I64, _I64, _I64, _P],
+    "cp25_mean_normalize": [_P, _I64, _P, _I64, _I64, _I64, _I64, _P],
+    "cp25_attn_causal": [_P, _P, _P, _P, _I, _I, _I, _I, _I, c_int64_p, c_int64_p, c_int64_p, c_int64_p, _F, _P],
 }
 
 
@@ -1430,3 +1436,142 @@ def lora_merge(w: torch.Tensor, a: torch.Tensor, b: torch.Tensor, scale: float) 
                              float(scale), _stream(w.device))
     _check("cp25_lora_merge", rc)
     return w
+
+
+# ----------------------------------------------------------------------------- Reason1 text encoder
+def _bf16_rows(name: str, t: torch.Tensor, cols: Optional[int] = None) -> None:
+    if t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1 or (cols is not None and t.shape[1] != cols):
+        want = "" if cols is None else f" of {cols} columns"
+        raise ValueError(f"{name} must be 2-D bf16 rows{want} with a contiguous last dim, got {t.dtype} {tuple(t.shape)}")
+
+
+def embed_gather(table: torch.Tensor, ids: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cp25_embed_gather: out[r, :D] = table[ids[r]] for the device table [V, D] bf16. ids: a HOST integer tensor of any
+    shape (n ids in all); every id is checked against [0, V) here, before anything is uploaded or launched, so no id
+    can make the kernel read outside the table. out: bf16 rows [n, >= D] (a new [n, D] tensor unless given)."""
+    lib = load_library()
+    _bf16_rows("table", table)
+    if not table.is_contiguous():
+        raise ValueError("embed_gather: the table must be contiguous")
+    if ids.is_cuda or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError("embed_gather: ids must be a host int32 / int64 tensor (they are validated before upload)")
+    V, D = table.shape
+    flat = ids.reshape(-1)
+    n = flat.numel()
+    if n == 0:
+        raise ValueError("embed_gather: no ids")
+    lo, hi = int(flat.min()), int(flat.max())
+    if lo < 0 or hi >= V:
+        raise ValueError(f"embed_gather: token ids span [{lo}, {hi}], outside the table's [0, {V})")
+    if out is None:
+        out = torch.empty((n, D), dtype=torch.bfloat16, device=table.device)
+    _bf16_rows("out", out)
+    if out.shape[0] != n or out.shape[1] < D or out.device != table.device:
+        raise ValueError(f"embed_gather: out {tuple(out.shape)} does not hold {n} rows of {D} on {table.device}")
+    dev_ids = flat.to(torch.int32).to(table.device)
+    _check("cp25_embed_gather", lib.cp25_embed_gather(_ptr(table), V, D, _ptr(dev_ids), _ptr(out), out.stride(0), n,
+                                                      _stream(table.device)))
+    return out
+
+
+def add_rmsnorm(x: torch.Tensor, y: Optional[torch.Tensor], weight: torch.Tensor, *, eps: float = 1e-6,
+                h_ld: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cp25_add_rmsnorm on rows x [n, D] bf16: x += y in place (y None: x unchanged), then returns
+    h = weight * bf16(x * (1 / sqrt(mean(x^2) + eps))) as rows [n, h_ld] (h_ld >= D, a multiple of 64, default D). With
+    h_ld > D column D is 1.0 and the rest 0: the bias column of a fused weight. out: the h buffer [n, h_ld] to use."""
+    lib = load_library()
+    _bf16_rows("x", x)
+    n, D = x.shape
+    if y is not None:
+        _bf16_rows("y", y, D)
+        if y.shape[0] != n:
+            raise ValueError(f"add_rmsnorm: y has {y.shape[0]} rows, x {n}")
+    if weight.dtype != torch.bfloat16 or weight.dim() != 1 or weight.shape[0] != D or not weight.is_contiguous():
+        raise ValueError(f"add_rmsnorm: weight must be contiguous bf16 [{D}]")
+    h_ld = D if h_ld is None else int(h_ld)
+    if out is None:
+        out = torch.empty((n, h_ld), dtype=torch.bfloat16, device=x.device)
+    _bf16_rows("out", out, h_ld)
+    if out.shape[0] != n or not out.is_contiguous():
+        raise ValueError(f"add_rmsnorm: out must be contiguous [{n}, {h_ld}]")
+    _check("cp25_add_rmsnorm", lib.cp25_add_rmsnorm(_ptr(x), x.stride(0), _ptr(y), 0 if y is None else y.stride(0),
+                                                    _ptr(weight), _ptr(out), h_ld, n, D, float(eps),
+                                                    _stream(x.device)))
+    return out
+
+
+def rope_qk(buf: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, *, heads: int) -> torch.Tensor:
+    """cp25_rope_qk, in place: rotate-half RoPE on the first `heads` 128-wide heads of the rows buf [n, ld] bf16 (the q
+    then the k heads of a fused QKV buffer), position = row mod L for the tables cos / sin [L, 128] bf16."""
+    lib = load_library()
+    _bf16_rows("buf", buf)
+    for name, t in (("cos", cos), ("sin", sin)):
+        _bf16_rows(name, t, 128)
+        if not t.is_contiguous() or t.shape != cos.shape or t.device != buf.device:
+            raise ValueError("rope_qk: cos and sin must be contiguous [L, 128] tables on buf's device")
+    n, L = buf.shape[0], cos.shape[0]
+    if n % L or heads * 128 > buf.shape[1]:
+        raise ValueError(f"rope_qk: {n} rows / {buf.shape[1]} columns do not fit L = {L}, {heads} heads")
+    _check("cp25_rope_qk", lib.cp25_rope_qk(_ptr(buf), buf.stride(0), n, L, int(heads), _ptr(cos), _ptr(sin),
+                                            _stream(buf.device)))
+    return buf
+
+
+def swiglu(gu: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cp25_swiglu: rows gu [n, 2 I] bf16 (gate | up) -> bf16(bf16(silu(gate)) * up) [n, I]."""
+    lib = load_library()
+    _bf16_rows("gu", gu)
+    n, I2 = gu.shape
+    if I2 % 2:
+        raise ValueError(f"swiglu: {I2} columns are not gate | up halves")
+    I = I2 // 2
+    if out is None:
+        out = torch.empty((n, I), dtype=torch.bfloat16, device=gu.device)
+    _bf16_rows("out", out, I)
+    if out.shape[0] != n:
+        raise ValueError(f"swiglu: out has {out.shape[0]} rows, gu {n}")
+    _check("cp25_swiglu", lib.cp25_swiglu(_ptr(gu), gu.stride(0), _ptr(out), out.stride(0), n, I, _stream(gu.device)))
+    return out
+
+
+def mean_normalize(x: torch.Tensor, out: torch.Tensor, col0: int = 0) -> torch.Tensor:
+    """cp25_mean_normalize: (x - mean) / (std + 1e-8) of the rows x [n, D] bf16, bf16 op by op, into columns
+    [col0, col0 + D) of the rows out [n, out_ld] bf16. Returns out."""
+    lib = load_library()
+    _bf16_rows("x", x)
+    _bf16_rows("out", out)
+    n, D = x.shape
+    if out.shape[0] != n or col0 < 0 or col0 + D > out.shape[1]:
+        raise ValueError(f"mean_normalize: columns [{col0}, +{D}) of {n} rows do not fit out {tuple(out.shape)}")
+    _check("cp25_mean_normalize", lib.cp25_mean_normalize(_ptr(x), x.stride(0), _ptr(out), out.stride(0), int(col0), n,
+                                                          D, _stream(x.device)))
+    return out
+
+
+def attn_causal(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: Optional[torch.Tensor] = None,
+                softmax_scale: Optional[float] = None) -> torch.Tensor:
+    """Causal grouped-query attention (cp25_attn_causal): q [B, L, Hq, 128], k / v [B, L, Hkv, 128] bf16 (any strides
+    with a contiguous head dim, e.g. column views of the fused QKV rows), Hq % Hkv == 0, L % 64 == 0; query i attends
+    keys j <= i of key/value head h // (Hq // Hkv). Returns [B, L, Hq, 128] bf16."""
+    lib = load_library()
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise ValueError("attn_causal expects bf16 q/k/v")
+    if q.dim() != 4 or k.dim() != 4 or tuple(v.shape) != tuple(k.shape) or k.shape[0] != q.shape[0] \
+            or k.shape[1] != q.shape[1] or k.shape[3] != q.shape[3]:
+        raise ValueError(f"attn_causal: q [B, L, Hq, D] and k / v [B, L, Hkv, D] expected, got q{tuple(q.shape)} "
+                         f"k{tuple(k.shape)} v{tuple(v.shape)}")
+    B, L, Hq, D = q.shape
+    Hkv = k.shape[2]
+    for t in (q, k, v):
+        if t.stride(3) != 1:
+            raise ValueError("head dim must be contiguous")
+    if out is None:
+        out = torch.empty((B, L, Hq, D), dtype=torch.bfloat16, device=q.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (B, L, Hq, D) or out.stride(3) != 1:
+        raise ValueError("attn_causal: out must be bf16 [B, L, Hq, D] with a contiguous head dim")
+    scale = float(D) ** -0.5 if softmax_scale is None else float(softmax_scale)
+    strides = [_i64x3((t.stride(0), t.stride(1), t.stride(2))) for t in (q, k, v, out)]
+    rc = lib.cp25_attn_causal(_ptr(q), _ptr(k), _ptr(v), _ptr(out), B, Hq, Hkv, L, D, *strides, scale,
+                              _stream(q.device))
+    _check("cp25_attn_causal", rc)
+    return out

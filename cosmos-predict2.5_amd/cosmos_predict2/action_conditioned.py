@@ -123,7 +123,8 @@ class ActionConditionedInference:
 
     def __init__(self, pipe: Optional[Video2WorldInference] = None, **pipe_kwargs):
         """pipe_kwargs go to Video2WorldInference (ckpt_path, tokenizer_path, lora_path / lora_alpha / lora_scale for a
-        LoRA post-trained net, ...)."""
+        LoRA post-trained net, text_encoder_path / text_tokenizer_path / offload_text_encoder for the on-device Reason1
+        encoder, ...)."""
         self.pipe = pipe or Video2WorldInference("2B/robot/action-cond", **pipe_kwargs)
 
     @torch.no_grad()

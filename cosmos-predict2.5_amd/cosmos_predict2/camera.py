@@ -151,7 +151,11 @@ class CameraInference:
                                         tokenizer_path=setup.tokenizer_path, state_t=setup.state_t,
                                         text_encoder=text_encoder, pixel_path=setup.pixel_path,
                                         lora_path=setup.lora_path, lora_alpha=setup.lora_alpha,
-                                        lora_scale=setup.lora_scale, **pipe_kwargs)
+                                        lora_scale=setup.lora_scale,
+                                        text_encoder_path=getattr(setup, "text_encoder_path", None),
+                                        text_tokenizer_path=getattr(setup, "text_tokenizer_path", None),
+                                        offload_text_encoder=getattr(setup, "offload_text_encoder", False),
+                                        **pipe_kwargs)
         self.pipe = pipe
         if not pipe.model.net_cfg.camera_dim:
             raise ValueError(f"CameraInference needs a camera-conditioned net (model {MODEL_NAME!r}), got "

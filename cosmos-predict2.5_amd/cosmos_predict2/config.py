@@ -83,6 +83,11 @@ class SetupArguments(pydantic.BaseModel):
     lora_path: Optional[str] = None
     lora_alpha: Optional[float] = None
     lora_scale: float = 1.0
+    # the on-device Reason1 text encoder (cosmos_predict2/text_encoder.py): a Qwen2.5-VL / Reason1 checkpoint (.pt,
+    # .safetensors or a folder of shards) and a local tokenizer directory; offload_text_encoder (above) parks its weights
+    # in host memory between encodes. None: the pipeline's synthetic encoder, or the text_encoder callable given
+    text_encoder_path: Optional[str] = None
+    text_tokenizer_path: Optional[str] = None
 
     @pydantic.model_validator(mode="before")
     @classmethod
@@ -92,7 +97,7 @@ class SetupArguments(pydantic.BaseModel):
                 raise ValueError(f"unknown model {data.get('model')}")
             if data.get("context_parallel_size") is None:
                 data["context_parallel_size"] = int(os.environ.get("WORLD_SIZE", "1"))
-            for k in ("checkpoint_path", "tokenizer_path", "lora_path"):
+            for k in ("checkpoint_path", "tokenizer_path", "lora_path", "text_encoder_path", "text_tokenizer_path"):
                 if data.get(k) is not None and not os.path.exists(data[k]):
                     raise ValueError(f"{k} '{data[k]}' does not exist.")
         return data

@@ -2,9 +2,10 @@
 
 Inference(args).generate(samples, output_dir) -> list of written paths. Videos are written as .mp4
 at 16 fps like the reference (inference.py:151-171, imaginaire/visualize/video.py), by this build's
-own H.264 I_PCM muxer (video_io.py: no ffmpeg ships in this image). Guardrails and
-the Reason1 text encoder are outside this build: prompt embeddings come from the
-pipeline's `text_encoder` callable.
+own H.264 I_PCM muxer (video_io.py: no ffmpeg ships in this image). Guardrails are outside this
+build. Prompt embeddings come from the pipeline's `text_encoder` callable:
+SetupArguments.text_encoder_path builds the on-device Reason1 encoder (text_encoder.py), an explicit
+`text_encoder=` wins, and without either the synthetic encoder stays.
 """
 from __future__ import annotations
 
@@ -38,7 +39,9 @@ class Inference:
                                          state_t=args.state_t, text_encoder=text_encoder,
                                          pixel_path=args.pixel_path, lora_path=args.lora_path,
                                          lora_alpha=args.lora_alpha, lora_scale=args.lora_scale,
-                                         stream_gemm=args.stream_gemm)
+                                         stream_gemm=args.stream_gemm, text_encoder_path=args.text_encoder_path,
+                                         text_tokenizer_path=args.text_tokenizer_path,
+                                         offload_text_encoder=args.offload_text_encoder)
         if self.rank0:
             Path(args.output_dir).mkdir(parents=True, exist_ok=True)
 

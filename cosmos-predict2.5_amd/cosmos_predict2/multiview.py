@@ -27,7 +27,8 @@ class MultiviewInference:
 
     def __init__(self, pipe: Optional[Video2WorldInference] = None, **pipe_kwargs):
         """pipe_kwargs go to Video2WorldInference (ckpt_path, tokenizer_path, lora_path / lora_alpha / lora_scale for a
-        LoRA post-trained net: cross_view_attn projections are adapter targets like self_attn's, ...)."""
+        LoRA post-trained net: cross_view_attn projections are adapter targets like self_attn's, text_encoder_path /
+        text_tokenizer_path / offload_text_encoder for the on-device Reason1 encoder, ...)."""
         pipe_kwargs.setdefault("model_name", "2B/auto/multiview")
         self.pipe = pipe or Video2WorldInference(**pipe_kwargs)
 

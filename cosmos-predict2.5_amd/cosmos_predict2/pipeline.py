@@ -5,10 +5,11 @@ Mirrors cosmos_predict2/_src/predict2/inference/video2world.py:
   as a uint8 tensor here: no mp4 demuxer ships in this image), Video2WorldInference :236-820
   (_get_data_batch_input :317-383, generate_vid2world :385-580, generate_autoregressive_from_batch
   :582-810).
-The Reason1 text encoder is outside the hot path: prompts are turned into
-[1, 512, 100352] embeddings by a pluggable `text_encoder` callable; the default one loads
-precomputed embeddings (torch.load(weights_only=True)) or, for benchmarking, derives seeded N(0, 1)
-embeddings from the prompt (`synthetic_text_encoder`).
+Prompts are turned into [1, 512, 100352] embeddings by a pluggable `text_encoder` callable:
+`text_encoder_path=` builds the on-device Reason1 encoder (cosmos_predict2/text_encoder.py: the
+language half of Qwen2.5-VL-7B on this build's GEMMs and HIP row / attention kernels), an explicit
+`text_encoder=` callable wins (e.g. one that loads precomputed embeddings), and without either the
+default derives seeded N(0, 1) embeddings from the prompt (`synthetic_text_encoder`, for benchmarking).
 """
 from __future__ import annotations
 
@@ -111,7 +112,8 @@ class Video2WorldInference:
                  net_cfg: Optional[DiTConfig] = None, sampler_cfg: Optional[SamplerConfig] = None,
                  weights_seed: int = 0, linear_precision: str = "bf16", attention_precision: str = "bf16",
                  pixel_path: str = "host", lora_path: Optional[str] = None, lora_alpha: Optional[float] = None,
-                 lora_scale: float = 1.0, stream_gemm: str = "tile256"):
+                 lora_scale: float = 1.0, stream_gemm: str = "tile256", text_encoder_path: Optional[str] = None,
+                 text_tokenizer_path: Optional[str] = None, offload_text_encoder: bool = False):
         """linear_precision: "bf16" (the reference's arithmetic) or "fp8" (the DiT block GEMMs as fp8
         MFMA, config 5's option; MinimalV1LVGDiT.set_linear_precision). attention_precision: "bf16", "fp8qk"
         (self-attention Q K^T on e4m3) or "fp8" (also P.V; MinimalV1LVGDiT.set_attention_precision).
@@ -123,7 +125,12 @@ class Video2WorldInference:
         ckpt_path that is itself in peft's layout (base_layer. keys plus adapters), which needs no lora_path.
         stream_gemm: the GEMM family of the streaming student's per-frame forward (MinimalV1LVGDiT.stream_gemm):
         "tile256" (default), "small" (the small-M kernels' exact form: the same bits) or "small_splitk" (their planned
-        K split); bf16 linears only."""
+        K split); bf16 linears only.
+        text_encoder_path: a Reason1 / Qwen2.5-VL checkpoint (.pt, .safetensors or a folder of shards) run by the
+        on-device encoder (text_encoder.build_text_encoder) with the tokenizer directory text_tokenizer_path;
+        offload_text_encoder parks its weights in host memory between encodes. An explicit text_encoder callable
+        wins; without either the synthetic encoder stays. The encoder's out_dim must equal the net's
+        crossattn_proj_in_channels (ValueError)."""
         if pixel_path not in ("host", "device"):
             raise ValueError(f"pixel_path must be 'host' or 'device', got {pixel_path!r}")
         self.pixel_path = pixel_path
@@ -137,6 +144,15 @@ class Video2WorldInference:
             import dataclasses
 
             scfg = dataclasses.replace(scfg, state_t=state_t)
+        emb_dim = ncfg.crossattn_proj_in_channels if ncfg.use_crossattn_projection else ncfg.crossattn_emb_channels
+        if text_encoder is not None and getattr(text_encoder, "out_dim", emb_dim) != emb_dim:
+            raise ValueError(f"text encoder out_dim {text_encoder.out_dim} != the net's crossattn_proj_in_channels "
+                             f"{emb_dim}")
+        if text_encoder is None and text_encoder_path is not None:  # a wrong width fails here, before the net is built
+            from .text_encoder import build_text_encoder
+
+            text_encoder = build_text_encoder(text_encoder_path, text_tokenizer_path, expect_dim=emb_dim,
+                                              device=self.device, offload=offload_text_encoder)
         self.context_parallel_size = context_parallel_size
         self.process_group = None
         if context_parallel_size > 1:
@@ -167,7 +183,6 @@ class Video2WorldInference:
         self.model.net.set_stream_gemm(stream_gemm)
         if self.process_group is not None:
             self.model.set_context_parallel_group(self.process_group)
-        emb_dim = ncfg.crossattn_proj_in_channels if ncfg.use_crossattn_projection else ncfg.crossattn_emb_channels
         self.text_encoder = text_encoder or (lambda p: synthetic_text_encoder(p, self.device, emb_dim))
         self.batch_size = 1
 

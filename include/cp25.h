@@ -698,6 +698,58 @@ int cp25_plucker_tokens(const float* w2c, const float* intrinsics, void* out, in
 int cp25_lora_merge(void* w, int64_t ldw, const float* a, const float* b, int64_t n_rows, int64_t k_cols, int rank,
                     float scale, hipStream_t stream);
 
+/* ---------------------------------------------------------------- Reason1 text encoder (text_ops.hip, attn_causal.hip)
+ * The language half of Qwen2.5-VL-7B as the reference's online text encoder runs it (text_encoders/text_encoder.py:
+ * 131-220): everything between the projections, which run on cp25_gemm_epi / cp25_gemm_sm_epi. Rows are n = B * L
+ * tokens, all activations bf16, every reference op one fp32 evaluation rounded to bf16 (NaN canonical). Leading
+ * dimensions are in elements and multiples of 8, base pointers 16-B aligned; -22 otherwise, before any launch.
+ *
+ * cp25_embed_gather: out[r, 0:D] = table[ids[r], :] for n rows (embed_tokens, reason1/networks/qwen2_5_vl.py:1226).
+ * table [V, D] contiguous, ids int32 on the device. The caller validates 0 <= id < V on the host; a row whose id is
+ * outside the table is written as zeros and reads nothing. */
+int cp25_embed_gather(const void* table, int64_t V, int64_t D, const int32_t* ids, void* out, int64_t out_ld, int64_t n,
+                      hipStream_t stream);
+
+/* The residual add and the next Qwen2RMSNorm (qwen2_5_vl.py:1135, :1141: `hidden_states = residual + hidden_states`,
+ * then Qwen2RMSNorm.forward, :215-232, eps 1e-6):
+ *   x[r, :] = bf16(x[r, :] + y[r, :])                       (written in place; y == NULL: x is left as it is)
+ *   h[r, c] = bf16(w[c] * bf16(x[r, c] * (1 / sqrt(sum_c x[r, c]^2 / D + eps))))
+ * with an fp32 sum in a fixed order and IEEE divide and sqrt. h has its own leading dimension h_ld >= D, a multiple of
+ * 64: if h_ld > D, h[r, D] = 1.0 and h[r, D + 1 : h_ld] = 0, so that a bias rides as column D of the next GEMM's
+ * weight. D % 8 == 0, D <= 8192 (-95 above), h_ld - D <= 2048. */
+int cp25_add_rmsnorm(void* x, int64_t x_ld, const void* y, int64_t y_ld, const void* w, void* h, int64_t h_ld,
+                     int64_t n, int64_t D, float eps, hipStream_t stream);
+
+/* 1-D rotate-half RoPE in place on heads 0 .. heads - 1 (128 wide each, the q heads then the k heads) of the fused
+ * QKV rows buf [n, ld]: position = row mod L, cos / sin [L, 128] bf16 tables made on the host,
+ *   q = bf16(bf16(q * cos) + bf16(rotate_half(q) * sin)),  rotate_half(q) = cat(-q[64:], q[:64])
+ * (apply_multimodal_rotary_pos_emb, qwen2_5_vl.py:662-700, whose three mrope sections all hold arange for a text-only
+ * prompt). n % L == 0, ld >= 128 heads. */
+int cp25_rope_qk(void* buf, int64_t ld, int64_t n, int L, int heads, const void* cos_t, const void* sin_t,
+                 hipStream_t stream);
+
+/* out[r, 0:I] = bf16(bf16(silu(gu[r, 0:I])) * gu[r, I:2I]) for the fused gate | up rows gu [n, ld >= 2 I]
+ * (Qwen2MLP.forward, qwen2_5_vl.py:647-659); silu(x) = x / (1 + exp(-x)) in fp32 as PyTorch's device kernel. I % 8 == 0. */
+int cp25_swiglu(const void* gu, int64_t ld, void* out, int64_t out_ld, int64_t n, int64_t I, hipStream_t stream);
+
+/* TextEncoder.mean_normalize (text_encoders/text_encoder.py:119-129) of one layer's hidden state x [n, D] into columns
+ * [col0, col0 + D) of out [n, out_ld] (the full_concat of :201-202), in the reference's op order on bf16 tensors:
+ *   m = bf16(sum x / D); s = bf16(sqrt(sum (x - mean)^2 / (D - 1))); out = bf16(bf16(x - m) / bf16(s + 1e-8))
+ * with fp32 sums in a fixed order, the std about the unrounded fp32 mean. 16 <= D <= 8192, D % 8 == 0, col0 % 8 == 0. */
+int cp25_mean_normalize(const void* x, int64_t x_ld, void* out, int64_t out_ld, int64_t col0, int64_t n, int64_t D,
+                        hipStream_t stream);
+
+/* Causal grouped-query attention, head dim 128 (anything else: -22): o[b, i, h] = softmax over keys j <= i of
+ * (q[b, i, h] . k[b, j, g] * softmax_scale) v[b, j, g], g = h / (Hq / Hkv). Replaces the causal flash attention of the
+ * Qwen2.5-VL decoder layers (qwen2_5_vl.py:829-940, Qwen2_5_VLFlashAttention2.forward) for a text-only prompt without a padding
+ * mask. q / o have Hq heads, k / v Hkv heads, Hq % Hkv == 0, L % 64 == 0. *_strides = (batch, token, head) element
+ * strides, multiples of 8 with token and head strides >= 128, so q / k / v can be column views of the fused QKV
+ * buffer. fp32 scores and sums, exact online row max, bf16 P; key tiles above the diagonal are not read and the
+ * diagonal tile is masked before the row max. No workspace, one launch. */
+int cp25_attn_causal(const void* q, const void* k, const void* v, void* o, int B, int Hq, int Hkv, int L, int D,
+                     const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                     const int64_t* o_strides, float softmax_scale, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
