@@ -134,6 +134,8 @@ SIGNATURES = {
     "cp25_unipc_step": [_P, _P, _P, _P, _P, _I64, ctypes.POINTER(UniPCParams), _P],
     "cp25_conv3d": [ctypes.POINTER(ctypes.c_void_p), _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                     _I, _I, _I, _I, _I, _I, _P],
+    "cp25_conv3d_clips": [ctypes.POINTER(ctypes.c_void_p), _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                          _I, _I, _I, _I, _I, _I, _I, _P],
     "cp25_rms_norm_silu": [_P, _P, _P, _I64, _I, _I, _P],
     "cp25_conv3d_select": [_I],
     "cp25_attn_cross_select": [_I],
@@ -1252,6 +1254,22 @@ def conv3d(frames, weight: torch.Tensor, bias: Optional[torch.Tensor], out: torc
                          Tout, KT, KH, KW, stride_t, stride_hw, pad[0], pad[1], pad[2], pad[3], int(upsample),
                          out_split, _stream(dev))
     _check("cp25_conv3d", rc)
+    return out
+
+
+def conv3d_clips(frames, n_clips: int, weight: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, *,
+                 Hin: int, Win: int, Cin: int, Cout: int, Tout: int, KT: int, KH: int, KW: int, stride_t: int = 1,
+                 stride_hw: int = 1, pad: tuple = (0, 0, 0, 0), upsample: bool = False, out_split: int = 0,
+                 residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """conv3d over n_clips independent clips in one launch (cp25_conv3d_clips, include/cp25.h): frames is n_clips runs
+    of (Tout / n_clips - 1) * stride_t + KT entries, each a clip's history and frames (None = a zero frame); out and
+    residual hold the clips' output frames clip-major."""
+    lib = load_library()
+    ptrs = (ctypes.c_void_p * max(len(frames), 1))(*[(_ptr(f) if f is not None else None) for f in frames])
+    rc = lib.cp25_conv3d_clips(ptrs, len(frames), int(n_clips), _ptr(weight), _ptr(bias), _ptr(residual), _ptr(out), Hin,
+                               Win, Cin, Cout, Tout, KT, KH, KW, stride_t, stride_hw, pad[0], pad[1], pad[2], pad[3],
+                               int(upsample), out_split, _stream(out.device))
+    _check("cp25_conv3d_clips", rc)
     return out
 
 

@@ -1137,14 +1137,15 @@ class MinimalV1LVGDiT:
         n, Bx, f = patch_rows.shape
         w = p["x_embedder.proj.1.weight"]
         if not cfg.view_condition_dim:
-            if rows_k128 and (Bx != 1 or f != 72 or patch_rows.stride(0) != 128 or patch_rows.stride(2) != 1):
-                raise ValueError("rows_k128: expected the [n, 1, 72] view of patchify(ld=128)'s [n, 128] buffer")
+            if rows_k128 and (f != 72 or patch_rows.stride(0) != 128 * Bx or patch_rows.stride(2) != 1
+                              or (Bx != 1 and patch_rows.stride(1) != 128)):
+                raise ValueError("rows_k128: expected the [n, Bx, 72] view of patchify(ld=128)'s [n * Bx, 128] buffer")
             if f > 128 or not N.gemm_supported(D, 128):
                 raise ValueError(f"x_embedder [{D}, {f}]: the own GEMM takes f <= 128 features and D % 256 == 0")
             # the zero-padded K = 128 operand of the own GEMM against the weight zero-padded to 128 columns (the same
             # sums as K = 72): rows from patchify(ld=128) are that operand already, other rows are copied into it
             if rows_k128:
-                a = torch.as_strided(patch_rows, (n, 128), (128, 1))
+                a = torch.as_strided(patch_rows, (n * Bx, 128), (128, 1))
             else:
                 a = torch.zeros((n * Bx, 128), dtype=BF16, device=self.device)
                 a[:, :f] = patch_rows.reshape(n * Bx, f)

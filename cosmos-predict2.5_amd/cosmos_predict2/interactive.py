@@ -14,16 +14,40 @@ as an array or an image path, not as a video file whose frame 0 is read.
 from __future__ import annotations
 
 import os
-from typing import Iterator, Optional, Tuple
+from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from .model import StreamingRun
+from .model import StreamingBatchRun, StreamingRun, session_seeds
 from .pipeline import _IMAGE_EXTENSIONS, Video2WorldInference, resize_input
 
 MODEL_NAME = "2B/robot/action-cond/streaming"
 CHUNK_ACTIONS = 12  # :217-227
+
+
+def chunk_seeds(seed, B: int, chunk: int) -> List[int]:
+    """The noise seeds of chunk `chunk` of B sessions: session b's chunk c draws seed_b + c, the one-session rule (seed
+    + chunk) per session. seed: an int (every session's seed_b) or B ints."""
+    return [s + int(chunk) for s in session_seeds(seed, B)]
+
+
+def check_batch_actions(actions_np, B: int, action_dim: int) -> np.ndarray:
+    """actions [B, N, action_dim] of B sessions, or ValueError."""
+    a = np.asarray(actions_np)
+    if a.ndim != 3 or a.shape[0] != B or a.shape[2] != action_dim:
+        raise ValueError(f"actions must be [{B}, N, {action_dim}] for {B} sessions, got {a.shape}")
+    return a
+
+
+def check_equal_frames(shapes: Sequence[Tuple[int, ...]]) -> Tuple[int, ...]:
+    """The one shape of every session's conditioning frame (after the resize), or ValueError."""
+    if not shapes:
+        raise ValueError("a batch needs at least one conditioning frame")
+    if any(tuple(s) != tuple(shapes[0]) for s in shapes):
+        raise ValueError(f"the sessions' conditioning frames differ in size after the resize: {[tuple(s) for s in shapes]} "
+                         "(pass resolution_hw)")
+    return tuple(shapes[0])
 
 
 class ActionStreamingInference:
@@ -49,6 +73,7 @@ class ActionStreamingInference:
             raise ValueError(f"text embeddings must be [Lctx, dim] or [1, Lctx, dim], got {tuple(text_embeddings.shape)}")
         self.text_embeddings = emb.to(self.pipe.device, torch.bfloat16)  # :238
         self._ctx = None  # the net's text context (projection + every block's cross-attention K / V), made once
+        self._ctx_batch = None  # ... replicated for the sessions of the batch entry points
 
     # ------------------------------------------------------------------ the input frame
     def _first_frame(self, first_frame_or_path, resolution_hw) -> torch.Tensor:
@@ -125,3 +150,60 @@ class ActionStreamingInference:
         """-> video [3, 1 + 12 (len(actions) // 12), H, W] fp32 in [-1, 1] (action_video2world_streaming.py:183-313)."""
         return torch.cat(list(self.stream_action_chunks(first_frame_or_path, actions_np, resolution_hw, num_steps, seed,
                                                         cache_frame_size)), dim=1)
+
+    # ------------------------------------------------------------------ B sessions in lock-step
+    @torch.no_grad()
+    def stream_action_chunks_batch(self, first_frames, actions_np: np.ndarray,
+                                   resolution_hw: Optional[Tuple[int, int]] = None, num_steps: int = 4, seed=1,
+                                   cache_frame_size: int = -1) -> Iterator[torch.Tensor]:
+        """stream_action_chunks for B independent sessions (parallel rollouts) through one sequence of launches: the VAE
+        encodes and decodes the B clips in lock-step and one per-frame forward serves all sessions
+        (model.StreamingBatchRun). first_frames: B arrays or image paths, of one size after the resize; actions_np
+        [B, N, action_dim]; seed an int or B ints, session b's chunk c drawing seed_b + c. Yields [B, 3, t, H, W] fp32
+        pieces: the input frames, then each chunk's 12 frames. The chunk rules are the one-session ones."""
+        pipe = self.pipe
+        model, dev = pipe.model, pipe.device
+        ncfg = model.net_cfg
+        first_frames = list(first_frames)
+        B = len(first_frames)
+        actions_np = check_batch_actions(actions_np, B, ncfg.action_dim)
+        session_seeds(seed, B)  # a seed list of the wrong length fails before any work
+        if ncfg.action_per_latent_frame != 4:
+            raise ValueError("the chunk loop is written for 4 actions per latent frame (12 actions -> 3 latent frames)")
+        K = len(model.config.selected_sampling_time)
+        n_steps = max(1, min(int(num_steps), K))
+        frames = [self._first_frame(f, resolution_hw) for f in first_frames]  # uint8 [3, H, W] each
+        check_equal_frames([tuple(f.shape) for f in frames])
+        frame = torch.stack(frames, 0)  # [B, 3, H, W]
+        yield frame.float()[:, :, None] / 128 - 1
+        on_device = pipe.pixel_path == "device"
+        if on_device:
+            frame = frame.to(dev)
+        T_lat = model.tokenizer.get_latent_num_frames(1 + CHUNK_ACTIONS)
+        for ar_idx in range(actions_np.shape[1] // CHUNK_ACTIONS):
+            gt = model.encode_conditioning(frame[:, :, None], 1, T_lat)  # [B, C, T_lat, h, w]
+            a = torch.from_numpy(np.ascontiguousarray(
+                actions_np[:, ar_idx * CHUNK_ACTIONS:(ar_idx + 1) * CHUNK_ACTIONS]))
+            a = a.float().to(dev, torch.bfloat16)
+            if self._ctx is None:
+                self._ctx = model.net.prepare_context(self.text_embeddings)
+            if self._ctx_batch is None or self._ctx_batch.B != B:
+                self._ctx_batch = StreamingBatchRun.batch_context(model, self._ctx, B)
+            run = StreamingBatchRun(model, gt, self._ctx_batch, a, seed=chunk_seeds(seed, B, ar_idx), n_steps=n_steps,
+                                    cache_frame_size=cache_frame_size)  # a fresh cache per chunk
+            while not run.done:
+                run.next_frame()
+            video = model.decode(run.latents()).clip(min=-1, max=1)  # [B, 3, 13, H, W] bf16
+            frame = ((1.0 + video[:, :, -1]) / 2 * 255.0).to(torch.uint8)
+            if not on_device:
+                frame = frame.cpu()
+            yield video[:, :, 1:].float().cpu()
+
+    @torch.no_grad()
+    def generate_action_streaming_batch(self, first_frames, actions_np: np.ndarray,
+                                        resolution_hw: Optional[Tuple[int, int]] = None, num_steps: int = 4, seed=1,
+                                        cache_frame_size: int = -1) -> torch.Tensor:
+        """-> videos [B, 3, 1 + 12 (N // 12), H, W] fp32 in [-1, 1]: session b is generate_action_streaming of
+        first_frames[b], actions_np[b] and seed_b."""
+        return torch.cat(list(self.stream_action_chunks_batch(first_frames, actions_np, resolution_hw, num_steps, seed,
+                                                              cache_frame_size)), dim=2)

@@ -23,7 +23,7 @@ cache (StreamingRun, generate_streaming_video; reference: interactive/models/act
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional
+from typing import Dict, List, Optional
 
 import numpy as np
 import torch
@@ -180,6 +180,22 @@ class Video2WorldModelRectifiedFlow:
                              f"{self.config.sampler!r}")
         run = StreamingRun(self, gt, ctx, actions, seed=seed, n_steps=n_steps, cache_frame_size=cache_frame_size,
                            net_fn=net_fn, init_noise=init_noise)
+        while not run.done:
+            run.next_frame()
+        return run.latents()
+
+    @torch.no_grad()
+    def generate_streaming_video_batch(self, gt: torch.Tensor, ctx, actions: torch.Tensor, *,
+                                       init_noise: Optional[torch.Tensor] = None, seed=0, n_steps: int = 4,
+                                       cache_frame_size: Optional[int] = None, net_fn=None) -> torch.Tensor:
+        """generate_streaming_video for B sessions in lock-step (StreamingBatchRun): gt [B, C, T, H, W], actions
+        [B, (T - 1) * action_per_latent_frame, action_dim], one text context [1, Lctx, proj_in] for all, seed an int or B
+        ints (or init_noise [B, C, T, H, W]). Returns the latents [B, C, T, H, W] bf16."""
+        if self.config.sampler != "dmd2_stream":
+            raise ValueError(f"generate_streaming_video_batch needs a 'dmd2_stream' sampler config, got "
+                             f"{self.config.sampler!r}")
+        run = StreamingBatchRun(self, gt, ctx, actions, seed=seed, n_steps=n_steps, cache_frame_size=cache_frame_size,
+                                net_fn=net_fn, init_noise=init_noise)
         while not run.done:
             run.next_frame()
         return run.latents()
@@ -728,3 +744,142 @@ class StreamingRun:
         """output_latents [1, C, T, H, W] bf16 (frames not yet generated are zero, as the reference initialises them)."""
         _, T, H, W = self.state_shape
         return from_patch_layout(self.out.view(-1, 64), T, H, W).unsqueeze(0)
+
+
+MAX_STREAM_BATCH = 16
+
+
+def session_seeds(seed, B: int) -> List[int]:
+    """The per-session noise seeds of a batch of B streaming sessions: an int gives every session that seed (each then
+    draws what the one-session run draws with it), a sequence must hold B ints."""
+    if isinstance(seed, (int, np.integer)):
+        return [int(seed)] * B
+    seeds = [int(s) for s in seed]
+    if len(seeds) != B:
+        raise ValueError(f"{len(seeds)} seeds for {B} sessions")
+    return seeds
+
+
+class StreamingBatchRun:
+    """B independent sessions of StreamingRun in lock-step: every session is at the same frame, and one forward_frame
+    over a K/V ring of batch B serves them all (parallel action rollouts from B conditioning frames under B action
+    sequences). gt [B, C, T, H, W], actions [B, (T - 1) * per, dim], one text context for all sessions; seed an int
+    (every session draws StreamingRun(seed=seed)'s noise) or B ints (session b draws StreamingRun(seed=seed[b])'s:
+    arch_invariant_rand((1, C, T, H, W), ..., seed_b)), or init_noise [B, C, T, H, W].
+    The state, the noise and the latents stay token-major, [T, hw, B, 64] bf16: stream_patchify and stream_x0_step are
+    elementwise over rows, so they run on the hw * B rows of a frame unchanged, and the patch rows come out as the
+    [hw, B, 72] forward_frame takes. The text context's per-block K / V are made once for one entry and replicated B
+    times (ContextCache of batch B). Session b computes what StreamingRun computes for its inputs; which launches keep
+    its bits at B > 1 is in DESIGN.md §6e.
+    net_fn(rows [hw, B, 72], t_B_1 [B, 1], geo, frame_idx, action [B, per, dim] | None, store) -> [hw, B, 64] fp32
+    replaces forward_frame (tests only)."""
+
+    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt: torch.Tensor, ctx, actions: torch.Tensor, *,
+                 seed=0, n_steps: int = 4, cache_frame_size: Optional[int] = None, net_fn=None,
+                 init_noise: Optional[torch.Tensor] = None):
+        cfg, ncfg, dev = model.config, model.net_cfg, model.device
+        times = [float(t) for t in cfg.selected_sampling_time]
+        if not 1 <= n_steps <= len(times):
+            raise ValueError(f"n_steps must be in 1 .. {len(times)} (the student schedule), got {n_steps}")
+        if gt.dim() != 5:
+            raise ValueError(f"gt must be the [B, C, T, H, W] conditioning latents, got {tuple(gt.shape)}")
+        B, C, T, H, W = gt.shape
+        if not 1 <= B <= MAX_STREAM_BATCH:
+            raise ValueError(f"a batch of {B} sessions: 1 .. {MAX_STREAM_BATCH} run in one forward")
+        per = ncfg.action_per_latent_frame
+        if (not per or actions.dim() != 3 or actions.shape[0] != B or actions.shape[1] != (T - 1) * per
+                or actions.shape[2] != ncfg.action_dim):
+            raise ValueError(f"actions must be [{B}, {(T - 1) * max(per, 1)}, {ncfg.action_dim}] for {B} sessions of {T} "
+                             f"latent frames of a per-latent-frame action net, got {tuple(actions.shape)}")
+        self.model, self.net_fn, self.n_steps, self.B = model, net_fn, n_steps, B
+        self.state_shape = (C, T, H, W)
+        self.geo = Geometry(T=T, Hp=H // 2, Wp=W // 2, tok0=0, n_tok=T * (H // 2) * (W // 2))
+        hw = self.geo.hw
+        bf = torch.bfloat16
+        if init_noise is None:
+            noise = [arch_invariant_rand((1, C, T, H, W), torch.float32, dev, s)[0] for s in session_seeds(seed, B)]
+        elif tuple(init_noise.shape) != (B, C, T, H, W):
+            raise ValueError(f"init_noise {tuple(init_noise.shape)} is not the state shape {(B, C, T, H, W)}")
+        else:
+            noise = [init_noise[b] for b in range(B)]
+        # [T, hw, B, 64]: session b's rows are StreamingRun's, interleaved per token
+        self.noise = torch.stack([to_patch_layout(n.to(dev, bf)).view(T, hw, 64) for n in noise], dim=2).contiguous()
+        self.out = torch.zeros((T, hw, B, 64), dtype=bf, device=dev)
+        self.out[0] = torch.stack([to_patch_layout(gt[b, :, :1].to(dev, bf)) for b in range(B)], dim=1)
+        self.actions = actions.to(dev).view(B, T - 1, per, ncfg.action_dim)
+        F = cfg.cache_frame_size if cache_frame_size is None else cache_frame_size
+        if F == 0 or F < -1:
+            raise ValueError(f"cache_frame_size must be -1 (the whole clip) or positive, got {F}")
+        self.cache_frames = T - 1 if F == -1 else min(F, T - 1)
+        self.cache = None
+        self.ctx = None
+        if net_fn is None:
+            self.ctx = self.batch_context(model, ctx, B)
+            self.cache = model.net.make_kv_cache(B, self.cache_frames, hw)
+        sc = lambda t: trigflow.stream_scaling(t, 0.0, cfg.trig_scaling, cfg.sigma_data, cfg.sigma_conditional)  # noqa: E731
+        self.sigma_data = float(cfg.sigma_data)
+
+        def t_rows(c_noise):  # one time for every session
+            return trigflow.net_timesteps(c_noise, ncfg.timestep_scale).to(dev).expand(B, 1).contiguous()
+
+        self.steps = []
+        for s in range(n_steps):
+            c_skip, c_out, c_in, c_noise = sc(times[s])
+            last = s == n_steps - 1
+            cos_n, sin_n = (0.0, 0.0) if last else trigflow.stream_renoise(times[s + 1])
+            self.steps.append(dict(c_skip=c_skip, c_out=c_out, c_in=c_in, cos_next=cos_n, sin_next=sin_n, last=last,
+                                   t_B_1=t_rows(c_noise)))
+        _, _, c_in0, c_noise0 = sc(0.0)
+        self.store_step = dict(c_in=c_in0, t_B_1=t_rows(c_noise0))
+        self.frame = 0
+
+    @staticmethod
+    def batch_context(model, ctx, B: int) -> ContextCache:
+        """The text context of B sessions: one entry's per-block K / V (a [1, Lctx, proj_in] embedding, projected here,
+        or a batch-1 ContextCache made once by the caller) replicated B times; a ContextCache of batch B passes."""
+        if isinstance(ctx, ContextCache) and ctx.B == B:
+            return ctx
+        one = ctx if isinstance(ctx, ContextCache) else model.net.prepare_context(ctx)
+        if one.B != 1:
+            raise ValueError(f"one text context serves every session; got a context of batch {one.B} for {B} sessions")
+        return ContextCache(B=B, k=[k.expand(B, -1, -1, -1).contiguous() for k in one.k],
+                            v=[v.expand(B, -1, -1, -1).contiguous() for v in one.v])
+
+    @property
+    def done(self) -> bool:
+        return self.frame >= self.geo.T
+
+    def _net(self, x: torch.Tensor, step: dict, frame: int, action, store: bool) -> torch.Tensor:
+        hw, B = self.geo.hw, self.B
+        rows = N.stream_patchify(x.view(hw * B, 64), step["c_in"], 0.0, None, ld=128).view(hw, B, -1)
+        if self.net_fn is not None:
+            return self.net_fn(rows, step["t_B_1"], self.geo, frame, action, store)
+        return self.model.net.forward_frame(rows, step["t_B_1"], self.ctx, self.geo, frame, action, store,
+                                            cache=self.cache, rows_k128=True)
+
+    @torch.no_grad()
+    def next_frame(self) -> int:
+        """Run every session's next frame (the first call: the conditioning frames' prefill); returns its index."""
+        if self.done:
+            raise RuntimeError("every frame of the clip has been generated")
+        f, n = self.frame, self.geo.hw * self.B
+        if f == 0:
+            self._net(self.out[0], self.store_step, 0, None, True)
+        else:
+            action = self.actions[:, f - 1]
+            noise = self.noise[f].view(n, 64)
+            x = noise
+            for s in self.steps:
+                net_out = self._net(x, s, f, action, False)
+                x = N.stream_x0_step(x, net_out.contiguous(), noise, c_skip=s["c_skip"], c_out=s["c_out"],
+                                     cos_next=s["cos_next"], sin_next=s["sin_next"], sigma_data=self.sigma_data,
+                                     last=s["last"], out=self.out[f].view(n, 64) if s["last"] else None)
+            self._net(self.out[f], self.store_step, f, action, True)
+        self.frame += 1
+        return f
+
+    @torch.no_grad()
+    def latents(self) -> torch.Tensor:
+        """output_latents [B, C, T, H, W] bf16 (frames not yet generated are zero)."""
+        _, T, H, W = self.state_shape
+        return torch.stack([from_patch_layout(self.out[:, :, b].reshape(-1, 64), T, H, W) for b in range(self.B)], 0)

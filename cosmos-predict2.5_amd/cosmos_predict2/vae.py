@@ -140,6 +140,25 @@ def init_vae_state_dict(seed: int = 0, device="cpu") -> Dict[str, torch.Tensor]:
     return out
 
 
+# ----------------------------------------------------------------------------- frame tables of several clips
+def clip_table_layout(Tc: int, stride_t: int, kt: int, n_clips: int, max_frames: int = MAX_FRAMES):
+    """The frame table of cp25_conv3d_clips for n_clips clips of Tc output frames each -> (Fc, launches).
+    Fc = (Tc - 1) * stride_t + kt entries per clip; clip c's run starts at entry c * Fc. launches: the clip ranges
+    (c0, c1) of the launches, in order, each of at most max_frames // Fc clips so that its table ((c1 - c0) * Fc entries,
+    clip c0's run first) fits. A single clip whose run alone overflows the table (Fc > max_frames) gets a launch range of
+    its own; the caller runs it on the one-clip path, which chunks over output frames."""
+    if Tc < 1 or stride_t < 1 or kt < 1 or n_clips < 1:
+        raise ValueError(f"clip_table_layout: Tc {Tc}, stride_t {stride_t}, kt {kt}, n_clips {n_clips}")
+    Fc = (Tc - 1) * stride_t + kt
+    per = max(1, max_frames // Fc)
+    return Fc, [(c0, min(n_clips, c0 + per)) for c0 in range(0, n_clips, per)]
+
+
+def clip_table_entry(clip: int, frame: int, tap: int, Fc: int, stride_t: int) -> int:
+    """The table entry output frame `frame` of clip `clip` reads at time tap `tap` (clip counted within its launch)."""
+    return clip * Fc + frame * stride_t + tap
+
+
 # ----------------------------------------------------------------------------- conv helpers
 class _Conv:
     """One convolution with device weights repacked [Cout][KT][KH][KW][Cin_pad]."""
@@ -159,18 +178,41 @@ class _Conv:
         self.cout, self.cin, self.cin_p, self.kt, self.kh, self.kw = cout, cin, cin_p, kt, kh, kw
 
     def __call__(self, frames: List[Optional[torch.Tensor]], Tout: int, H: int, W: int, *, stride_t=1, stride_hw=1,
-                 pad=(0, 0, 0, 0), upsample=False, out_split=0, residual=None) -> torch.Tensor:
+                 pad=(0, 0, 0, 0), upsample=False, out_split=0, residual=None, n_clips=1, out=None) -> torch.Tensor:
+        """frames: the frame table; Tout output frames. n_clips > 1: `frames` is n_clips equal runs (each clip's causal
+        history, then its frames) and Tout counts every clip's output frames, clip-major (cp25_conv3d_clips)."""
         dev = self.w.device
         Hu, Wu = (2 * H, 2 * W) if upsample else (H, W)
         Ho = (Hu + pad[0] + pad[2] - self.kh) // stride_hw + 1
         Wo = (Wu + pad[1] + pad[3] - self.kw) // stride_hw + 1
-        if out_split:
+        if out is not None:
+            pass  # (a slice of a batch's output)
+        elif out_split:
             out = torch.empty((2 * Tout, Ho, Wo, out_split), dtype=BF16, device=dev)
         else:
             out = torch.empty((Tout, Ho, Wo, self.cout), dtype=BF16, device=dev)
+        f = 2 if out_split else 1
+        if n_clips > 1:
+            kw = dict(Hin=H, Win=W, Cin=self.cin_p, Cout=self.cout, KT=self.kt, KH=self.kh, KW=self.kw,
+                      stride_t=stride_t, stride_hw=stride_hw, pad=pad, upsample=upsample, out_split=out_split)
+            if Tout % n_clips or len(frames) % n_clips:
+                raise ValueError(f"{Tout} output frames / {len(frames)} table entries do not split into {n_clips} clips")
+            Tc, L = Tout // n_clips, len(frames) // n_clips
+            Fc, launches = clip_table_layout(Tc, stride_t, self.kt, n_clips)
+            if L < Fc:
+                raise ValueError(f"a clip brings {L} frames, {Tc} output frames read {Fc}")
+            for c0, c1 in launches:
+                o = out[f * c0 * Tc: f * c1 * Tc]
+                r = None if residual is None else residual[f * c0 * Tc: f * c1 * Tc]
+                if Fc > MAX_FRAMES:  # (c1 = c0 + 1) one clip overflows the table: the one-clip path chunks its frames
+                    self(frames[c0 * L: c0 * L + Fc], Tc, H, W, stride_t=stride_t, stride_hw=stride_hw, pad=pad,
+                         upsample=upsample, out_split=out_split, residual=r, out=o)
+                    continue
+                tab = [fr for c in range(c0, c1) for fr in frames[c * L: c * L + Fc]]
+                N.conv3d_clips(tab, c1 - c0, self.w, self.b, o, Tout=(c1 - c0) * Tc, residual=r, **kw)
+            return out
         # the kernel takes at most MAX_FRAMES input frames per launch: chunk the output frames
         per = max(1, (MAX_FRAMES - self.kt) // stride_t + 1)
-        f = 2 if out_split else 1
         for t0 in range(0, Tout, per):
             t1 = min(Tout, t0 + per)
             fr = frames[t0 * stride_t: (t1 - 1) * stride_t + self.kt]
@@ -192,7 +234,12 @@ class _FeatCache:
 
 
 class WanVAE:
-    """Encoder/decoder over channels-last clips; B = 1 (the sampler's batch)."""
+    """Encoder/decoder over channels-last clips. B clips of one size run in lock-step through one sequence of launches:
+    an activation is [B * T, H, W, C], clip-major (clip b's T frames at rows b T .. b T + T - 1), so the per-pixel and
+    per-frame kernels (rms_norm_silu, vae_attn) see B * T frames, and every convolution gets a frame table of B runs,
+    clip b's causal history followed by clip b's frames (cp25_conv3d_clips; _Conv splits the clips over several launches
+    where the runs overflow one table). The feature cache holds B * k frames per slot the same way. B = 1 is the one-clip
+    path: the same launches as before the batch existed."""
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], device="cuda", dim=96, z_dim=16,
                  temporal_window: int = 16):
@@ -215,6 +262,7 @@ class WanVAE:
         self.mean, self.inv_std = mean, 1.0 / std
         self.cp_group = None  # decode shards latent rows over this group (see module docstring)
         self._band = None  # (group, rank, world) while a banded decode runs
+        self._nb = 1  # clips in flight (set by encode / decode for the call)
 
     # ---------------------------------------------------------------- context-parallel bands
     def _halo(self, x: torch.Tensor) -> torch.Tensor:
@@ -237,6 +285,65 @@ class WanVAE:
             xh[:, R + 1].zero_()
         return xh
 
+    # ---------------------------------------------------------------- clip-major helpers
+    def _tail(self, x: torch.Tensor, k: int) -> torch.Tensor:
+        """A copy of the last k frames of every clip (all of them where a clip has fewer), clip-major."""
+        if self._nb == 1:
+            return x[-k:].clone()
+        return x.unflatten(0, (self._nb, -1))[:, -k:].clone(memory_format=torch.contiguous_format).flatten(0, 1)
+
+    def _last(self, x: torch.Tensor) -> torch.Tensor:
+        """Every clip's last frame, [B, H, W, C]."""
+        if self._nb == 1:
+            return x[-1:]
+        return x.unflatten(0, (self._nb, -1))[:, -1]
+
+    def _cat_t(self, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+        """Per clip: a's frames, then b's."""
+        if self._nb == 1:
+            return torch.cat([a, b], 0)
+        return torch.cat([a.unflatten(0, (self._nb, -1)), b.unflatten(0, (self._nb, -1))], 1).flatten(0, 1)
+
+    def _cat_clips(self, parts: List[torch.Tensor]) -> torch.Tensor:
+        """Clip-major pieces [nb * k_i, ...] of consecutive time ranges -> [nb * sum k_i, ...], clip-major."""
+        if self._nb == 1:
+            return torch.cat(parts, 0)
+        return torch.cat([p.unflatten(0, (self._nb, -1)) for p in parts], 1).flatten(0, 1)
+
+    def _table(self, prev: Optional[torch.Tensor], x: torch.Tensor, n_pre: int = 2) -> List[Optional[torch.Tensor]]:
+        """The frame table of a causal conv: per clip n_pre history entries (the clip's cached frames `prev`, zero
+        frames = None in front where it has fewer) and then the clip's frames of x."""
+        nb = self._nb
+        if nb == 1:
+            if prev is None:
+                return [None] * n_pre + _frames(x)
+            return [None] * (n_pre - prev.shape[0]) + _frames(prev) + _frames(x)
+        T = x.shape[0] // nb
+        kp = 0 if prev is None else prev.shape[0] // nb
+        tab: List[Optional[torch.Tensor]] = []
+        for b in range(nb):
+            tab += [None] * (n_pre - kp)
+            tab += [prev[b * kp + j] for j in range(kp)]
+            tab += [x[b * T + j] for j in range(T)]
+        return tab
+
+    def _push(self, cache: _FeatCache, x: torch.Tensor):
+        """The feat_cache rule of a CausalConv3d (wan2pt1.py:206-219): the slot takes every clip's last CACHE_T frames
+        (topped up with the previous entry's last frame); returns the previous entry."""
+        i = cache.idx
+        prev = cache.slots.get(i)
+        if self._nb == 1:
+            cache_x = x[-CACHE_T:].clone()
+            if cache_x.shape[0] < 2 and prev is not None:
+                cache_x = torch.cat([prev[-1:], cache_x], 0)
+        else:
+            cache_x = self._tail(x, CACHE_T)
+            if cache_x.shape[0] // self._nb < 2 and prev is not None:
+                cache_x = self._cat_t(self._last(prev), cache_x)
+        cache.slots[i] = cache_x
+        cache.idx += 1
+        return prev
+
     # ---------------------------------------------------------------- building blocks
     def _causal(self, name, x, cache: Optional[_FeatCache], H, W):
         """CausalConv3d 3x3x3 (pad 1) with the feat_cache rule (wan2pt1.py:206-219)."""
@@ -245,24 +352,12 @@ class WanVAE:
         if self._band is not None:
             x = self._halo(x)
             H, pad = H + 2, (0, 1, 0, 1)
-        T = x.shape[0]
-        prev = None
-        if cache is not None:
-            i = cache.idx
-            prev = cache.slots.get(i)
-            cache_x = x[-CACHE_T:].clone()
-            if cache_x.shape[0] < 2 and prev is not None:
-                cache_x = torch.cat([prev[-1:], cache_x], 0)
-            cache.slots[i] = cache_x
-            cache.idx += 1
-        pre: List[Optional[torch.Tensor]] = [None, None]
-        if prev is not None:
-            pre = [None] * (2 - prev.shape[0]) + _frames(prev)
-        return conv(pre + _frames(x), T, H, W, pad=pad)
+        prev = self._push(cache, x) if cache is not None else None
+        return conv(self._table(prev, x), x.shape[0], H, W, pad=pad, n_clips=self._nb)
 
     def _res(self, p, x, cache, H, W, cin, cout):
         if cin != cout:
-            h = self.convs[p + ".shortcut"](_frames(x), x.shape[0], H, W)
+            h = self.convs[p + ".shortcut"](_frames(x), x.shape[0], H, W, n_clips=self._nb)
         else:
             h = x
         y = N.rms_norm_silu(x, self.gammas[p + ".residual.0"], silu=True)
@@ -276,22 +371,14 @@ class WanVAE:
         if self._band is not None:
             x = self._halo(x)
             H, pad = H + 2, (0, 1, 0, 1)
-        T = x.shape[0]
-        i = cache.idx
-        prev = cache.slots.get(i)
-        cache_x = x[-CACHE_T:].clone()
-        if cache_x.shape[0] < 2 and prev is not None:
-            cache_x = torch.cat([prev[-1:], cache_x], 0)
-        cache.slots[i] = cache_x
-        cache.idx += 1
-        pre: List[Optional[torch.Tensor]] = [None, None] if prev is None else [None] * (2 - prev.shape[0]) + _frames(prev)
-        return conv(pre + _frames(x), T, H, W, pad=pad, residual=residual)
+        prev = self._push(cache, x)
+        return conv(self._table(prev, x), x.shape[0], H, W, pad=pad, residual=residual, n_clips=self._nb)
 
     def _attn(self, p, x, H, W):
         C = x.shape[-1]
         T = x.shape[0]
         y = N.rms_norm_silu(x, self.gammas[p + ".norm"], silu=False)
-        qkv = self.convs[p + ".to_qkv"](_frames(y), T, H, W)  # [T, H, W, 3C]
+        qkv = self.convs[p + ".to_qkv"](_frames(y), T, H, W, n_clips=self._nb)  # [T, H, W, 3C]
         qkv = qkv.view(T, H * W, 3 * C)
         q, k, v = qkv[:, :, :C], qkv[:, :, C:2 * C], qkv[:, :, 2 * C:]
         if self._band is not None:  # K/V of the whole frame: every band's rows, in row order
@@ -305,7 +392,7 @@ class WanVAE:
         # cp25_vae_attn (fp32 scores, bf16 P), no score matrix in HBM
         o = N.vae_attn(q, k, v)
         o = o.view(T, H, W, C)
-        return self.convs[p + ".proj"](_frames(o), T, H, W, residual=x)
+        return self.convs[p + ".proj"](_frames(o), T, H, W, residual=x, n_clips=self._nb)
 
     def _resample(self, p, kind, x, cache, H, W):
         T = x.shape[0]
@@ -316,13 +403,14 @@ class WanVAE:
                 cache.slots[i] = "Rep"
                 cache.idx += 1
             else:
-                cache_x = x[-CACHE_T:].clone()
-                if cache_x.shape[0] < 2 and not isinstance(prev, str):
-                    cache_x = torch.cat([prev[-1:], cache_x], 0)
-                if cache_x.shape[0] < 2 and isinstance(prev, str):
-                    cache_x = torch.cat([torch.zeros_like(cache_x), cache_x], 0)
-                pre = [None, None] if isinstance(prev, str) else [None] * (2 - prev.shape[0]) + _frames(prev)
-                x = self.convs[p + ".time_conv"](pre + _frames(x), T, H, W, out_split=x.shape[-1])
+                nb = self._nb
+                cache_x = self._tail(x, CACHE_T)
+                if cache_x.shape[0] // nb < 2 and not isinstance(prev, str):
+                    cache_x = self._cat_t(self._last(prev), cache_x)
+                if cache_x.shape[0] // nb < 2 and isinstance(prev, str):
+                    cache_x = self._cat_t(torch.zeros_like(cache_x), cache_x)
+                tab = self._table(None if isinstance(prev, str) else prev, x)
+                x = self.convs[p + ".time_conv"](tab, T, H, W, out_split=x.shape[-1], n_clips=nb)
                 cache.slots[i] = cache_x
                 cache.idx += 1
         T = x.shape[0]
@@ -333,10 +421,10 @@ class WanVAE:
             y = conv(_frames(xh), T, H + 2, W, pad=(-1, 1, -1, 1), upsample=True)
             H, W = 2 * H, 2 * W
         elif kind.startswith("upsample"):
-            y = conv(_frames(x), T, H, W, pad=(1, 1, 1, 1), upsample=True)
+            y = conv(_frames(x), T, H, W, pad=(1, 1, 1, 1), upsample=True, n_clips=self._nb)
             H, W = 2 * H, 2 * W
         else:
-            y = conv(_frames(x), T, H, W, stride_hw=2, pad=(0, 0, 1, 1))
+            y = conv(_frames(x), T, H, W, stride_hw=2, pad=(0, 0, 1, 1), n_clips=self._nb)
             H, W = H // 2, W // 2
         if kind == "downsample3d" and cache is not None:
             i = cache.idx
@@ -345,10 +433,11 @@ class WanVAE:
                 cache.slots[i] = y.clone()
                 cache.idx += 1
             else:
-                cache_x = y[-1:].clone()
-                fr = [prev[-1]] + _frames(y)
-                tout = (len(fr) - 3) // 2 + 1
-                y = self.convs[p + ".time_conv"](fr, tout, H, W, stride_t=2)
+                nb = self._nb
+                cache_x = self._tail(y, 1)
+                fr = self._table(self._last(prev), y, n_pre=1)
+                tout = (len(fr) // nb - 3) // 2 + 1  # per clip
+                y = self.convs[p + ".time_conv"](fr, nb * tout, H, W, stride_t=2, n_clips=nb)
                 cache.slots[i] = cache_x
                 cache.idx += 1
         return y, H, W
@@ -386,85 +475,113 @@ class WanVAE:
 
     @torch.no_grad()
     def encode(self, video: torch.Tensor) -> torch.Tensor:
-        """video [1, 3, T, H, W] (bf16 in [-1, 1]) -> mu [1, 16, 1 + (T-1)//4, H/8, W/8] bf16."""
-        assert video.shape[0] == 1, "batch 1"
-        _, C, T, H, W = video.shape
-        x = torch.zeros((T, H, W, 16), dtype=BF16, device=self.device)  # channels padded 3 -> 16
-        x[..., :C] = video[0].to(self.device, BF16).permute(1, 2, 3, 0)
-        return self._encode_clip(x)
+        """video [B, 3, T, H, W] (bf16 in [-1, 1]) -> mu [B, 16, 1 + (T-1)//4, H/8, W/8] bf16; the B clips run in
+        lock-step (class docstring), each with the bits of its own B = 1 call."""
+        if video.dim() != 5 or video.shape[0] < 1:
+            raise ValueError(f"encode takes a [B, C, T, H, W] video, got {tuple(video.shape)}")
+        B, C, T, H, W = video.shape
+        x = torch.zeros((B * T, H, W, 16), dtype=BF16, device=self.device)  # channels padded 3 -> 16
+        x.view(B, T, H, W, 16)[..., :C] = video.to(self.device, BF16).permute(0, 2, 3, 4, 1)
+        return self._encode_clip(x, B)
 
     @torch.no_grad()
     def encode_u8(self, video_u8: torch.Tensor) -> torch.Tensor:
-        """uint8 device video [1, 3, T, H, W] (any strides) -> mu, as encode(video.to(bf16) / 127.5 - 1.0): the
-        normalisation, the channels-last permute and the 3 -> 16 channel pad are one kernel (cp25_u8_to_clip)
+        """uint8 device video [B, 3, T, H, W] (any strides) -> mu, as encode(video.to(bf16) / 127.5 - 1.0): the
+        normalisation, the channels-last permute and the 3 -> 16 channel pad are one kernel (cp25_u8_to_clip) per clip
         writing the encoder's input clip."""
-        if video_u8.dim() != 5 or video_u8.shape[0] != 1 or video_u8.dtype != torch.uint8:
-            raise ValueError(f"encode_u8 takes a uint8 [1, C, T, H, W] video, got {video_u8.dtype} {tuple(video_u8.shape)}")
-        return self._encode_clip(N.u8_to_clip(video_u8[0].to(self.device)))
+        if video_u8.dim() != 5 or video_u8.shape[0] < 1 or video_u8.dtype != torch.uint8:
+            raise ValueError(f"encode_u8 takes a uint8 [B, C, T, H, W] video, got {video_u8.dtype} {tuple(video_u8.shape)}")
+        B = video_u8.shape[0]
+        if B == 1:
+            return self._encode_clip(N.u8_to_clip(video_u8[0].to(self.device)))
+        _, _, T, H, W = video_u8.shape
+        x = torch.empty((B * T, H, W, 16), dtype=BF16, device=self.device)
+        for b in range(B):
+            N.u8_to_clip(video_u8[b].to(self.device), out=x[b * T:(b + 1) * T])
+        return self._encode_clip(x, B)
 
-    def _encode_clip(self, x: torch.Tensor) -> torch.Tensor:
-        """x [T, H, W, 16] bf16 channels-last clip -> mu [1, 16, Tl, H/8, W/8]."""
-        T, H, W, _ = x.shape
+    def _encode_clip(self, x: torch.Tensor, nb: int = 1) -> torch.Tensor:
+        """x [nb * T, H, W, 16] bf16 channels-last clips (clip-major) -> mu [nb, 16, Tl, H/8, W/8]."""
+        _, H, W, _ = x.shape
+        T = x.shape[0] // nb
+        x5 = x.view(nb, T, H, W, 16)
         cache = _FeatCache()
         tw = self.temporal_window
-        chunks = [x[:1]]
+        chunks = [x5[:, :1]]
         n_iter = 1 + (T - 1) // tw
         for i in range(1, n_iter):
-            chunks.append(x[1 + tw * (i - 1): 1 + tw * i])
+            chunks.append(x5[:, 1 + tw * (i - 1): 1 + tw * i])
         if (T - 1) % tw:
-            chunks.append(x[1 + tw * (n_iter - 1):])
+            chunks.append(x5[:, 1 + tw * (n_iter - 1):])
         outs = []
-        for ch in chunks:
-            cache.idx = 0
-            o, h, w = self._encoder(ch.contiguous(), cache, H, W)
-            outs.append(o)
-        out = torch.cat(outs, 0)
-        mu = self.convs["conv1"](_frames(out), out.shape[0], h, w)  # [Tl, h, w, 16]
+        self._nb = nb
+        try:
+            for ch in chunks:
+                cache.idx = 0
+                o, h, w = self._encoder(ch.contiguous().flatten(0, 1), cache, H, W)
+                outs.append(o)
+            out = self._cat_clips(outs)
+            mu = self.convs["conv1"](_frames(out), out.shape[0], h, w, n_clips=nb)  # [nb * Tl, h, w, 16]
+        finally:
+            self._nb = 1
         mu = (mu - self.mean) * self.inv_std
-        return mu.permute(3, 0, 1, 2).unsqueeze(0).contiguous()
+        return mu.unflatten(0, (nb, -1)).permute(0, 4, 1, 2, 3).contiguous()
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor) -> torch.Tensor:
-        """latent [1, 16, T, h, w] -> video [1, 3, 1 + 4 (T-1), 8h, 8w] bf16."""
-        return self._decode_clip(z).permute(3, 0, 1, 2).unsqueeze(0).contiguous()
+        """latent [B, 16, T, h, w] -> video [B, 3, 1 + 4 (T-1), 8h, 8w] bf16; the B clips run in lock-step (class
+        docstring), each with the bits of its own B = 1 call. The banded (context-parallel) decode takes B = 1."""
+        return self._decode_clip(z).unflatten(0, (z.shape[0], -1)).permute(0, 4, 1, 2, 3).contiguous()
 
     @torch.no_grad()
     def decode_u8(self, z: torch.Tensor, layout: str = "THWC") -> torch.Tensor:
         """latent -> uint8 video, [T, H, W, 3] ("THWC") or [1, 3, T, H, W] ("NCTHW"): decode's channels-last
-        result quantised by cp25_clip_to_u8 (trunc(clamp((v + 1) / 2, 0, 1) * 255)), with no NCTHW or fp32 copy."""
+        result quantised by cp25_clip_to_u8 (trunc(clamp((v + 1) / 2, 0, 1) * 255)), with no NCTHW or fp32 copy.
+        B > 1 latents give [B, T, H, W, 3] or [B, 3, T, H, W], clip b as its own B = 1 call."""
         from .pixels import clip_to_uint8
 
         if layout not in ("THWC", "NCTHW"):
             raise ValueError(f"layout must be 'THWC' or 'NCTHW', got {layout!r}")
-        return clip_to_uint8(self._decode_clip(z), layout)
+        B = z.shape[0]
+        clips = self._decode_clip(z)
+        if B == 1:
+            return clip_to_uint8(clips, layout)
+        outs = [clip_to_uint8(c, layout) for c in clips.unflatten(0, (B, -1))]
+        return torch.stack(outs, 0) if layout == "THWC" else torch.cat(outs, 0)
 
     def _decode_clip(self, z: torch.Tensor) -> torch.Tensor:
-        """latent [1, 16, T, h, w] -> channels-last video [Tp, H, W, 3] bf16 (bands gathered under CP)."""
-        assert z.shape[0] == 1, "batch 1"
-        _, C, T, h, w = z.shape
-        zl = z[0].to(self.device, BF16).permute(1, 2, 3, 0).contiguous()  # [T, h, w, 16]
+        """latent [B, 16, T, h, w] -> channels-last video [B * Tp, H, W, 3] bf16, clip-major (bands gathered under CP)."""
+        if z.dim() != 5 or z.shape[0] < 1:
+            raise ValueError(f"decode takes a [B, 16, T, h, w] latent, got {tuple(z.shape)}")
+        nb, C, T, h, w = z.shape
+        zl = z.to(self.device, BF16).permute(0, 2, 3, 4, 1).contiguous().flatten(0, 1)  # [nb * T, h, w, 16]
         zl = zl / self.inv_std + self.mean
         group = self.cp_group
         r, n = cpx.cp_rank_world(group)
         if n > 1 and h % n == 0:
+            if nb > 1:
+                raise ValueError(f"the banded (context-parallel) decode takes one clip, got a batch of {nb}")
             self._band = (group, r, n)
             zl = zl[:, r * (h // n):(r + 1) * (h // n)]
             h = h // n
+        self._nb = nb
         try:
-            x = self.convs["conv2"](_frames(zl.contiguous()), T, h, w)
+            x = self.convs["conv2"](_frames(zl.contiguous()), nb * T, h, w, n_clips=nb)
+            x5 = x.unflatten(0, (nb, T))
             cache = _FeatCache()
             outs = []
             for i in range(T):
                 cache.idx = 0
-                o, H, W = self._decoder(x[i: i + 1].contiguous(), cache, h, w)
+                o, H, W = self._decoder(x5[:, i: i + 1].contiguous().flatten(0, 1), cache, h, w)
                 outs.append(o)
-            video = torch.cat(outs, 0)  # [Tp, H, W, 3] (this rank's band of H rows when banded)
+            video = self._cat_clips(outs)  # [nb * Tp, H, W, 3] (this rank's band of H rows when banded)
             if self._band is not None:
                 allv = torch.empty((n,) + tuple(video.shape), dtype=video.dtype, device=video.device)
                 cpx.all_gather_into(allv, video, group)
                 video = allv.permute(1, 0, 2, 3, 4).reshape(video.shape[0], n * video.shape[1], *video.shape[2:])
         finally:
             self._band = None
+            self._nb = 1
         return video
 
 
@@ -489,11 +606,12 @@ class Wan2pt1VAEInterface:
         return self.model.decode(latent).to(in_dtype)
 
     def encode_u8(self, video_u8: torch.Tensor) -> torch.Tensor:
-        """uint8 [1, 3, T, H, W] device video -> bf16 latent (WanVAE.encode_u8)."""
+        """uint8 [B, 3, T, H, W] device video -> bf16 latent (WanVAE.encode_u8)."""
         return self.model.encode_u8(video_u8)
 
     def decode_u8(self, latent: torch.Tensor, layout: str = "THWC") -> torch.Tensor:
-        """latent -> uint8 device video [T, H, W, 3] ("THWC") or [1, 3, T, H, W] ("NCTHW") (WanVAE.decode_u8)."""
+        """latent -> uint8 device video [T, H, W, 3] ("THWC") or [1, 3, T, H, W] ("NCTHW"); [B, ...] latents with
+        B > 1 give [B, T, H, W, 3] or [B, 3, T, H, W] (WanVAE.decode_u8)."""
         return self.model.decode_u8(latent, layout)
 
     def get_latent_num_frames(self, num_pixel_frames: int) -> int:

@@ -28,6 +28,10 @@ constexpr int kBM = 128;  // output pixels per workgroup (4 waves x 32)
 struct ConvArgs {
   const unsigned short* frames[kMaxFrames];  // input frames [Hin][Win][Cin]; nullptr = zeros
   int n_frames;
+  int Tc, Fc;  // clips: output frame to is frame to % Tc of clip to / Tc, whose run of the table starts at (to / Tc) * Fc
+               // (one clip: Tc = Tout, Fc = n_frames, so the entry is to * stride_t + kt)
+  int Tc_inv;  // 65536 / Tc + 1: to / Tc = (to * Tc_inv) >> 16 exactly for to < Tout <= kMaxFrames (no integer division
+               // in front of a workgroup's first load)
   const unsigned short* w;  // [Cout][KT][KH][KW][Cin]
   const unsigned short* bias;  // [Cout] bf16 or nullptr
   const unsigned short* residual;  // same layout as out or nullptr
@@ -91,13 +95,16 @@ __global__ void __launch_bounds__(256) conv_igemm_kernel(ConvArgs a) {
     }
   }
 
+  // this output frame's first table entry: frame to % Tc of clip to / Tc (one clip: to * stride_t)
+  const int clip = (to * a.Tc_inv) >> 16;
+  const int fi0 = clip * a.Fc + (to - clip * a.Tc) * a.stride_t;
   auto load_stage = [&](int ks) {
     const int tap = ks / kc_per_tap;
     const int c0 = (ks % kc_per_tap) * BK;
     const int kw = tap % a.KW;
     const int kh = (tap / a.KW) % a.KH;
     const int kt = tap / (a.KW * a.KH);
-    const int fi = to * a.stride_t + kt;
+    const int fi = fi0 + kt;
     const unsigned short* fr = (fi < a.n_frames) ? a.frames[fi] : nullptr;
 #pragma unroll
     for (int i = 0; i < A_PER_T; ++i) {
@@ -377,9 +384,11 @@ __global__ void __launch_bounds__(64 * NW, 1) conv3x3_halo_kernel(ConvArgs a) {
   // argument load inside the loop is an SMEM access, and with one in flight the compiler's LDS waits degrade to
   // lgkmcnt(0)
   const unsigned short* frk[3];
+  const int clip = (to * a.Tc_inv) >> 16;  // to / Tc
+  const int fi0 = clip * a.Fc + (to - clip * a.Tc) * a.stride_t;  // frame to % Tc of clip to / Tc
 #pragma unroll
   for (int kt = 0; kt < 3; ++kt) {
-    const int fi = to * a.stride_t + kt;
+    const int fi = fi0 + kt;
     frk[kt] = (kt < a.KT && fi < a.n_frames) ? a.frames[fi] : nullptr;
   }
   auto issue = [&](int st, int buf) __attribute__((always_inline)) {
@@ -626,17 +635,28 @@ static int g_conv_select = [] {
   return (e && !std::strcmp(e, "tap")) ? 1 : 0;
 }();
 
-extern "C" int cp25_conv3d(const void* const* frames, int n_frames, const void* weight, const void* bias,
-                           const void* residual, void* out, int Hin, int Win, int Cin, int Cout, int Tout, int KT,
-                           int KH, int KW, int stride_t, int stride_hw, int pad_top, int pad_left, int pad_bottom,
-                           int pad_right, int upsample, int out_split, hipStream_t stream) {
+extern "C" int cp25_conv3d_clips(const void* const* frames, int n_frames, int n_clips, const void* weight,
+                                 const void* bias, const void* residual, void* out, int Hin, int Win, int Cin,
+                                 int Cout, int Tout, int KT, int KH, int KW, int stride_t, int stride_hw, int pad_top,
+                                 int pad_left, int pad_bottom, int pad_right, int upsample, int out_split,
+                                 hipStream_t stream) {
   if (n_frames < 1 || n_frames > kMaxFrames || !weight || !out || Tout < 1) return CP25_ERR_INVAL;
   if (Cin % 16 != 0 || Cin <= 0 || Cout <= 0) return CP25_ERR_DTYPE;
-  if ((Tout - 1) * stride_t + KT > n_frames) return CP25_ERR_INVAL;
+  if (n_clips < 1 || Tout % n_clips != 0 || stride_t < 1 || KT < 1) return CP25_ERR_INVAL;
+  const int Tc = Tout / n_clips;
+  const int64_t Fc = (int64_t)(Tc - 1) * stride_t + KT;  // table entries of one clip
+  if (n_clips == 1) {
+    if (Fc > n_frames) return CP25_ERR_INVAL;  // one clip may bring more frames than it reads
+  } else if (n_clips * Fc > kMaxFrames || n_clips * Fc != n_frames) {
+    return CP25_ERR_INVAL;
+  }
   if (out_split > 0 && (Cout != 2 * out_split || out_split % 4)) return CP25_ERR_INVAL;
   ConvArgs a;
   for (int i = 0; i < kMaxFrames; ++i) a.frames[i] = i < n_frames ? (const unsigned short*)frames[i] : nullptr;
   a.n_frames = n_frames;
+  a.Tc = Tc;
+  a.Tc_inv = 65536 / Tc + 1;  // Tc <= Tout <= n_frames <= kMaxFrames
+  a.Fc = n_clips == 1 ? n_frames : (int)Fc;
   a.w = (const unsigned short*)weight;
   a.bias = (const unsigned short*)bias;
   a.residual = (const unsigned short*)residual;
@@ -679,6 +699,15 @@ extern "C" int cp25_conv3d(const void* const* frames, int n_frames, const void* 
   CONV_CASE(64, 1) CONV_CASE(64, 2) CONV_CASE(64, 3) CONV_CASE(64, 4)
 #undef CONV_CASE
   return CP25_ERR_DTYPE;
+}
+
+// one clip: the n_clips = 1 case of the same kernels (to / Tc = 0, to % Tc = to: the entry is to * stride_t + kt)
+extern "C" int cp25_conv3d(const void* const* frames, int n_frames, const void* weight, const void* bias,
+                           const void* residual, void* out, int Hin, int Win, int Cin, int Cout, int Tout, int KT,
+                           int KH, int KW, int stride_t, int stride_hw, int pad_top, int pad_left, int pad_bottom,
+                           int pad_right, int upsample, int out_split, hipStream_t stream) {
+  return cp25_conv3d_clips(frames, n_frames, 1, weight, bias, residual, out, Hin, Win, Cin, Cout, Tout, KT, KH, KW,
+                           stride_t, stride_hw, pad_top, pad_left, pad_bottom, pad_right, upsample, out_split, stream);
 }
 
 extern "C" int cp25_conv3d_select(int mode) {

@@ -584,6 +584,19 @@ int cp25_conv3d(const void* const* frames, int n_frames, const void* weight, con
                 int stride_hw, int pad_top, int pad_left, int pad_bottom, int pad_right, int upsample, int out_split,
                 hipStream_t stream);
 
+/* cp25_conv3d over n_clips independent clips of Tc = Tout / n_clips output frames each, in one launch (the VAE on a
+ * batch of clips in lock-step). The table holds n_clips runs of Fc = (Tc - 1) * stride_t + KT entries, clip c's run at
+ * entries c * Fc .. c * Fc + Fc - 1 (its causal history, then its frames; NULL = a zero frame). Output frame `to`
+ * belongs to clip to / Tc and reads entries (to / Tc) * Fc + (to % Tc) * stride_t + kt, so no window straddles two
+ * clips; out is [Tout][Ho][Wo][Cout] with clip c's frames at c * Tc .. (with out_split, [2 * Tout] and 2 c Tc ..), and
+ * residual likewise. Everything else is cp25_conv3d, which is the n_clips = 1 case of the same kernels (one clip may
+ * bring more than Fc frames; the surplus is not read). Returns -22 before any launch, writing nothing, if
+ * n_clips < 1, Tout % n_clips != 0, or (n_clips > 1) n_clips * Fc > 24 or n_clips * Fc != n_frames. */
+int cp25_conv3d_clips(const void* const* frames, int n_frames, int n_clips, const void* weight, const void* bias,
+                      const void* residual, void* out, int Hin, int Win, int Cin, int Cout, int Tout, int KT, int KH,
+                      int KW, int stride_t, int stride_hw, int pad_top, int pad_left, int pad_bottom, int pad_right,
+                      int upsample, int out_split, hipStream_t stream);
+
 /* Kernel choice of cp25_conv3d for the 3x3 stride-1 convs: 0 (default) the LDS-halo kernel where it applies, 1 the
  * per-tap implicit GEMM everywhere (A/B runs and tests; same arithmetic up to summation order), 2 the round-2 halo
  * kernel with 4 waves per workgroup (one per SIMD; bit-identical to 0, which runs 8). Returns the previous mode. The
