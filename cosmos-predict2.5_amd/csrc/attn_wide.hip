@@ -27,17 +27,21 @@
 // S(u) (per query block 8 v_exp_f32 and 4 bf16 packs: 12 kNQ instructions, placed by the compile-time gap plan below),
 // the operand reads two fragments ahead (a ring of three) and the LDS-DMA pieces.
 //
-// The LDS keeps attn_fwd_m16's image: 64-key K and V tiles in 288-B rows, two buffers each, and ONE workgroup barrier
-// per 64 keys. Iteration t is the two half stages u = 2 t + 1 (A) and 2 t + 2 (B): both read V(t) (key step 0, then 1)
-// and K(t + 1) (key blocks 0-1, then 2-3) and nothing else, so the ten DMA pieces of K(t + 2) and V(t + 1) go to the
-// two buffers the previous iteration read. Each wave drains its pieces (vmcnt(0)) before the closing barrier, which
-// publishes them. The DMA is the bounds-checked buffer form: rows past the last key read as zeros, so the ragged tile
-// and the virtual tile the last iteration prefetches need no path of their own; scores of keys >= Lk are set to -inf
-// before their softmax (P = 0 exactly), per half stage.
+// The LDS keeps attn_fwd_m16's image of a 64-key K or V tile (288-B rows); a buffer is TWO such images back to back,
+// two buffers each of K and V (147 456 B), and there is ONE buffer flip, DMA batch, vmcnt(0) drain and workgroup
+// barrier per 128 keys (round 17; round 13 had one per 64). Iteration t is the four half stages u = 4 t + 1 .. 4 t + 4:
+// stage st reads V(2 t + (st >> 1)) (key step st & 1) and K(2 t + 1 + (st >> 1)) (key blocks 2 (st & 1), + 1) and
+// nothing else, so K's buffers are cut one tile later than V's: iteration t reads the K buffer {K(2 t + 1), K(2 t + 2)}
+// and the V buffer {V(2 t), V(2 t + 1)}, and the 18 DMA pieces a wave moves (9 of K(2 t + 3), K(2 t + 4), 9 of
+// V(2 t + 2), V(2 t + 3)) go to the two buffers the previous iteration read. Each wave drains its pieces (vmcnt(0))
+// before the closing barrier, which publishes them. The DMA is the bounds-checked buffer form: rows past the last key
+// read as zeros, so the ragged tile and the virtual tiles past it need no path of their own; scores of keys >= Lk
+// are set to -inf before their softmax (P = 0 exactly), per half stage.
 //
-// Prologue: K(0), K(1), V(0) by DMA, then iteration t = -1 without its P.V and without stage A's softmax: Q K^T(0),
-// softmax S(0), Q K^T(1). The loop then runs t = 0 .. ntk - 1; the last iteration's Q K^T and stage-B softmax work on
-// a virtual tile whose results no one reads.
+// Prologue: K(0) (as the last image of K buffer 1), K(1), K(2), V(0), V(1) by DMA, then "iteration -1" of two stages
+// without P.V and without the first softmax: Q K^T(0), softmax S(0), Q K^T(1). The loop then runs ceil(ntk / 2)
+// iterations. Its last Q K^T and softmax work on a virtual tile no one reads, and with an odd tile count its last two
+// stages on a virtual V tile too: P = 0 exactly on zero V rows, which adds +0 to O^T and to the row sums.
 #include "attn_common.h"
 
 namespace cp25attn {
@@ -50,7 +54,7 @@ static_assert(kWqThreads == 4 * 64, "one wave per SIMD");
 // ---- the gap plan of one half stage: 17 kNQ MFMA slots. Slot m < kNQ: the row sum of query block m; then fragment
 // f = (m - kNQ) / kNQ (0-7: V^T block db = f of P.V; 8-15: K fragment j = f - 8, key block j & 1, d step j >> 1) x query
 // block (m - kNQ) % kNQ. A fragment's first MFMA is its "read gap": the reads of the fragment kAheadWq later follow
-// it, and (stage A) DMA piece d < 10 rides in the read gap of fragment d, its M0 set in the gap before. The softmax's
+// it, and DMA slot d rides in the read gap of the iteration's fragment d, its M0 set in the gap before. The softmax's
 // 12 kNQ instructions (per query block e0 e1 c0 e2 e3 c1 e4 e5 c2 e6 e7 c3) take the other gaps in slot order. One
 // v_exp fills a gap's issue slots (8 of the MFMA's 16 cycles).
 constexpr int wq_stage(int nq) { return 17 * nq; }
@@ -69,11 +73,50 @@ constexpr int wq_sm_count(int nq) {
   return n;
 }
 static_assert(wq_sm_count(5) == 60 && wq_sm_count(6) == 72, "every softmax instruction has a gap");
-// DMA piece d (0-4: K(t + 2), 5-9: V(t + 1)) in the gap after iteration slot M (stage A), or -1; its M0 one gap earlier
-constexpr int wq_dma_at(int nq, int M) {
-  return M < wq_stage(nq) && wq_read_gap(nq, M) && wq_frag(nq, M) < 10 ? wq_frag(nq, M) : -1;
+// 64-key tiles per loop iteration (one buffer flip, one DMA batch, one vmcnt(0) drain and one workgroup barrier each):
+// two, so the LDS holds two buffers of two 64-key images each for K and for V. -DCP25_WQ_PARENT_LOOP (tools/lab
+// only, never libcp25.so) rebuilds round 13's loop for A/B runs: one tile per iteration, the fifth DMA piece on
+// waves 0-1 alone.
+// Two further lab switches, each measured inside the run-to-run spread on its own and so not in the product
+// (profiles/r17/attn_k128/SUMMARY.md): -DCP25_WQ_NO_PAD_FETCH gives the lanes of the row padding an offset outside
+// every descriptor, so they fetch nothing; -DCP25_WQ_GAP_RSRC makes the tile descriptors by adds in the last three
+// gaps of the iteration before, under MFMAs, instead of at the head of the iteration behind the barrier.
+#ifdef CP25_WQ_PARENT_LOOP
+#define CP25_WQ_ITER_TILES 1
+#undef CP25_WQ_NO_PAD_FETCH
+#undef CP25_WQ_GAP_RSRC
+#endif
+#ifndef CP25_WQ_ITER_TILES
+#define CP25_WQ_ITER_TILES 2
+#endif
+constexpr int wq_iter_tiles(int) { return CP25_WQ_ITER_TILES; }
+#ifdef CP25_WQ_NO_PAD_FETCH
+constexpr bool kWqPadFetch = false;
+#else
+constexpr bool kWqPadFetch = true;
+#endif
+#ifdef CP25_WQ_GAP_RSRC
+constexpr bool kWqHeadRsrc = false;
+#else
+constexpr bool kWqHeadRsrc = true;
+#endif
+constexpr int kWqImg = kKBuf16;  // one 64-key image
+static_assert(kKBuf16 == kVBuf16, "K and V images of one size");
+// DMA slots of a wave per iteration: one tile, 5 K + 5 V pieces (the fifth on waves 0-1 only: 18 pieces a tile over
+// 4 waves); two tiles, 9 + 9: pieces 0-15 of both images on every wave, pieces 16-17 of image 0 on waves 0-1 and of
+// image 1 on waves 2-3
+constexpr int wq_dma_n(int it) { return it == 1 ? 10 : 18; }
+// DMA slot d (K first, then V) in the gap after iteration slot M, or -1: the read gaps of the iteration's first
+// wq_dma_n fragments; its M0 one gap earlier
+constexpr int wq_dma_at(int nq, int it, int M) {
+  const int st = M / wq_stage(nq), m = M % wq_stage(nq);
+  if (st >= 2 * it || !wq_read_gap(nq, m)) return -1;
+  const int F = 16 * st + wq_frag(nq, m);
+  return F < wq_dma_n(it) ? F : -1;
 }
-constexpr int wq_m0_at(int nq, int M) { return wq_dma_at(nq, M + 1); }
+constexpr int wq_m0_at(int nq, int it, int M) { return wq_dma_at(nq, it, M + 1); }
+// a lane offset no tile's descriptor covers: the bounds-checked load writes zeros and fetches nothing
+constexpr int kWqNoFetch = 0x7ffffff0;
 
 // the bounds-checked buffer descriptor of one K or V tile (rows past the tile's last key read as zero)
 __device__ __forceinline__ u32x4 tile_rsrc(const char* base, int64_t sl, int rows) {
@@ -88,9 +131,15 @@ template <int kNQ, int kMode, int kTail = 0>
 __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   static_assert(kMode == 0 || kMode == 1, "kMode: 0 fixed shift, 1 zero shift");
   static_assert(kNQ >= 4 && kNQ <= 6, "query blocks per wave");
-  __shared__ __attribute__((aligned(16))) char smem[kLds16];
+  constexpr int kIT = wq_iter_tiles(kNQ);  // 64-key tiles per iteration
+  static_assert(kIT == 1 || kIT == 2, "tiles per iteration");
+  constexpr int kBuf = kIT * kWqImg;       // one buffer: kIT images back to back
+  constexpr int VB0 = 2 * kBuf;            // K buffers 0, 1, then V buffers 0, 1
+  static_assert(4 * kBuf <= 163840, "the CU's LDS");
+  __shared__ __attribute__((aligned(16))) char smem[4 * kBuf];
   constexpr bool kInit = kMode != 1;  // the shift rides in the Q K^T chains' initial C
-  constexpr int KB1 = kKBuf16, VB0 = 2 * kKBuf16;
+  constexpr int kPar = kIT == 1 ? 1 : 0;  // iteration T reads the K buffer (T + kPar) & 1 and the V buffer T & 1
+  constexpr int kND = wq_dma_n(kIT);
   constexpr int kR = kRingWq;
   constexpr int kRowsW = 16 * kNQ;    // query rows per wave
   constexpr int kRowsG = 4 * kRowsW;  // per workgroup
@@ -117,48 +166,81 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   const char* const kbase = (const char*)(a.k + b * a.k_sb + h * a.k_sh + (int64_t)key0 * a.k_sl);
   const char* const vbase = (const char*)(a.v + b * a.v_sb + h * a.v_sh + (int64_t)key0 * a.v_sl);
 
-  // ---- LDS-DMA: piece p = wave + 4 j of a tile (18 per tile: waves 0-1 move 5, waves 2-3 move 4) is tile bytes
-  // [1024 p, +1024) of the 64 x 288-B image, lane l the 16 B at 16 l of it: row bb / 288, column bb % 288 (columns
-  // >= 256 are the row padding and re-read the tile's first 16 B), attn_fwd_m16's dma_tile. Bounds-checked buffer loads:
-  // rows past the tile's last key (the ragged tile, the virtual tiles past Lk) read as zero.
+  // ---- LDS-DMA: piece p of a 64-key image (18 per image) is image bytes [1024 p, +1024) of the 64 x 288-B image, lane
+  // l the 16 B at 16 l of it: row bb / 288, column bb % 288, attn_fwd_m16's dma_tile. Every wave moves the pieces
+  // wave + 4 j, j = 0..3; the fifth offset is piece 16 + (wave & 1): of image 0 on waves 0-1 and of image 1 on waves
+  // 2-3, so a wave moves 9 pieces of the two images of a buffer (one tile per iteration: piece 16 + wave on waves 0-1).
+  // Bounds-checked buffer loads: rows past the tile's last key (the ragged tile, the virtual tiles past Lk) read as
+  // zero. The lanes of the row padding (columns >= 256, which no fragment read touches: K reads and the transposed V
+  // reads end at byte 255 of a row) re-read the tile's first 16 B (lab: an offset outside every descriptor).
+  const int wave5 = kIT == 1 ? wave : (wave & 1);  // the fifth piece's lane block
+  const int img5 = kIT == 1 ? 0 : (wave >> 1);     // and its image
   int dk[5], dv[5];
 #pragma unroll
   for (int j = 0; j < 5; ++j) {
-    const int bb = 1024 * (wave + 4 * j) + 16 * lane;
+    const int bb = 1024 * ((j < 4 ? wave : wave5) + 4 * j) + 16 * lane;
     const int row = bb / kKStride16, cb = bb - row * kKStride16;
-    dk[j] = cb < 2 * kD ? row * (int)(a.k_sl * 2) + cb : 0;
-    dv[j] = cb < 2 * kD ? row * (int)(a.v_sl * 2) + cb : 0;
+    dk[j] = cb < 2 * kD ? row * (int)(a.k_sl * 2) + cb : (kWqPadFetch ? 0 : kWqNoFetch);
+    dv[j] = cb < 2 * kD ? row * (int)(a.v_sl * 2) + cb : (kWqPadFetch ? 0 : kWqNoFetch);
   }
   const unsigned lds_wave = (unsigned)(uintptr_t)(lds_char_ptr)smem + 1024u * (unsigned)wave;
+  // the fifth piece's destination: byte 16384 + 1024 (wave & 1) of image img5 (the 16384 rides in the M0 add)
+  const unsigned lds_wave5 =
+      (unsigned)(uintptr_t)(lds_char_ptr)smem + 1024u * (unsigned)wave5 + (unsigned)kWqImg * (unsigned)img5;
   auto k_rsrc = [&](int t) __attribute__((always_inline)) {
     return tile_rsrc(kbase + (int64_t)t * kKBlk * a.k_sl * 2, a.k_sl, min(Lk - t * kKBlk, kKBlk));
   };
   auto v_rsrc = [&](int t) __attribute__((always_inline)) {
     return tile_rsrc(vbase + (int64_t)t * kKBlk * a.v_sl * 2, a.v_sl, min(Lk - t * kKBlk, kKBlk));
   };
-  // M0 = the wave's LDS destination of a piece (an SALU write; the load that reads it is at least one MFMA later)
+  // M0 = the wave's LDS destination of a piece (an SALU write; the load that reads it is at least one MFMA later). The
+  // add writes SCC: declared, or the compiler keeps a compare's SCC live across the statement (it did, in the prologue:
+  // a descriptor's row-count select read the add's carry and the tile landed as zeros)
   auto set_m0 = [&](unsigned dst, auto OFFC) __attribute__((always_inline)) {
-    asm volatile("s_add_u32 m0, %0, %1" ::"s"(dst), "i"(decltype(OFFC)::value) : "memory");
+    asm volatile("s_add_u32 m0, %0, %1" ::"s"(dst), "i"(decltype(OFFC)::value) : "memory", "scc");
   };
   auto dma_load = [&](const u32x4& rs, int off) __attribute__((always_inline)) {
     asm volatile("buffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(off), "s"(rs) : "memory");
   };
-  // one whole tile (prologue): pieces j = 0..4 into LDS byte dst + 4096 j (dst includes the wave's 1024 wave)
-  auto dma_tile = [&](const u32x4& rs, const int* offs, unsigned dst) __attribute__((always_inline)) {
-    static_for<5>([&](auto JC) __attribute__((always_inline)) {
-      constexpr int j = decltype(JC)::value;
-      if (j < 4 || wave < 2) {
-        set_m0(dst, std::integral_constant<int, 4096 * j>{});
-        asm volatile("s_nop 0" ::: "memory");
-        dma_load(rs, offs[j]);
-      }
+  // prologue: one piece into LDS byte dst + OFFC (the nops: the descriptor's SALU writes -> the load that reads it)
+  auto dma_piece = [&](const u32x4& rs, int off, unsigned dst, auto OFFC) __attribute__((always_inline)) {
+    set_m0(dst, OFFC);
+    asm volatile("s_nop 4" ::: "memory");
+    dma_load(rs, off);
+  };
+  // prologue: pieces 0-15 of one image whose LDS byte offset is at (every wave its four)
+  auto dma_img = [&](const u32x4& rs, const int* offs, unsigned at) __attribute__((always_inline)) {
+    static_for<4>([&](auto JC) __attribute__((always_inline)) {
+      dma_piece(rs, offs[decltype(JC)::value], lds_wave + at, std::integral_constant<int, 4096 * decltype(JC)::value>{});
     });
   };
+  // prologue: the kIT images of the buffer at LDS byte offset at, tiles t0 .. t0 + kIT - 1, with their pieces 16-17
+  auto dma_buf = [&](auto rsrc, const int* offs, int t0, unsigned at) __attribute__((always_inline)) {
+    if constexpr (kIT == 1) {
+      const u32x4 rs = rsrc(t0);
+      dma_img(rs, offs, at);
+      if (wave < 2) dma_piece(rs, offs[4], lds_wave + at, std::integral_constant<int, 16384>{});
+    } else {
+      const u32x4 rs0 = rsrc(t0), rs1 = rsrc(t0 + 1);
+      dma_img(rs0, offs, at);
+      dma_img(rs1, offs, at + (unsigned)kWqImg);
+      if (wave < 2) dma_piece(rs0, offs[4], lds_wave5 + at, std::integral_constant<int, 16384>{});
+      else dma_piece(rs1, offs[4], lds_wave5 + at, std::integral_constant<int, 16384>{});
+    }
+  };
 
-  // K(0), K(1), V(0) first: their flight overlaps the Q loads and the q normalisation
-  dma_tile(k_rsrc(0), dk, lds_wave);
-  dma_tile(k_rsrc(1), dk, lds_wave + KB1);
-  dma_tile(v_rsrc(0), dv, lds_wave + VB0);
+  // K(0), K(1) .. K(kIT), V(0) .. V(kIT - 1) first: their flight overlaps the Q loads and the q normalisation. The
+  // prologue reads K(0) as the last image of the K buffer "iteration -1" reads; iteration 0 reads K(1) .. K(kIT) from
+  // the other K buffer and V(0) .. V(kIT - 1) from V buffer 0
+  constexpr unsigned kK0At = (unsigned)(((kPar + 1) & 1) * kBuf + (kIT - 1) * kWqImg);
+  {
+    const u32x4 rs = k_rsrc(0);
+    dma_img(rs, dk, kK0At);
+    // (waves 0-1: lds_wave5 of image 0 is lds_wave)
+    if (wave < 2) dma_piece(rs, dk[4], lds_wave + kK0At, std::integral_constant<int, 16384>{});
+  }
+  dma_buf(k_rsrc, dk, 1, (unsigned)((kPar & 1) * kBuf));
+  dma_buf(v_rsrc, dv, 0, (unsigned)VB0);
 
   // ---- Q fragments Q[16 qb + c][32 s + 8 g .. +7] of rows row_w + 16 qb + c ----
   bf16x8 qa[kNQ][4];
@@ -310,20 +392,23 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   unsigned pk[4];
   unsigned k_cur = 0, v_cur = 0;  // this iteration's K(t + 1) / V(t) read bases
 
-  // fragment F of an iteration (stage F / 16, f = F % 16): f < 8 the V^T fragment (db = f, key step = stage: two
-  // transposed reads), f >= 8 the K fragment (key block 2 stage + ((f - 8) & 1), d step (f - 8) >> 1)
+  // fragment F of an iteration (stage F / 16, f = F % 16; stage st works on image st >> 1 of the iteration's K and V
+  // buffers, half st & 1 of it): f < 8 the V^T fragment (db = f, key step = st & 1: two transposed reads), f >= 8 the K
+  // fragment (key block 2 (st & 1) + ((f - 8) & 1), d step (f - 8) >> 1)
   auto issue = [&](auto FC, auto SLOTC) __attribute__((always_inline)) {
     constexpr int F = decltype(FC)::value, slot = decltype(SLOTC)::value;
     constexpr int st = F / 16, f = F % 16;
+    constexpr int img = (st >> 1) * kWqImg, hs = st & 1;
+    static_assert(img + kWqImg <= 65536, "ds_read offset field");
     (void)ring;
     (void)k_cur;
     (void)v_cur;
     if constexpr (f >= 8) {
       constexpr int j = f - 8;
-      constexpr int off = (2 * st + (j & 1)) * 16 * kKStride16 + 64 * (j >> 1);
+      constexpr int off = img + (2 * hs + (j & 1)) * 16 * kKStride16 + 64 * (j >> 1);
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[slot]) : "v"(k_cur), "i"(off));
     } else {
-      constexpr int off = 32 * st * kVStride16 + 32 * f;
+      constexpr int off = img + 32 * hs * kVStride16 + 32 * f;
       s16x4 lo, hi;
       asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(v_cur), "i"(off));
       asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(v_cur), "i"(off + 16 * kVStride16));
@@ -350,39 +435,124 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
     }
   };
 
-  // One iteration t: stage A (u = 2 t + 1) then stage B (u = 2 t + 2). Stage ST's row sums and P.V read P[ST] and
-  // V(t)'s key step ST; its Q K^T reads K(t + 1)'s key blocks 2 ST, 2 ST + 1 and writes S[ST]; its softmax reads
-  // S[1 - ST] and writes P[1 - ST]. FULL: the loop's iteration; else the prologue (t = -1: no P.V, no stage-A softmax,
-  // no DMA).
+  // The DMA's wave-uniform state (SGPRs): the descriptors of the tiles iteration t fetches, K(kIT (t + 1) + 1 + i) and
+  // V(kIT (t + 1) + i), i < kIT (rk5 / rv5: the fifth piece's image). Past the last tile: an empty range, the pieces
+  // land as zeros. The product computes them at the head of the iteration. The lab form (kWqHeadRsrc false) makes them
+  // by adds from a running base and row count in three steps, which the loop takes for iteration t + 1 in the last three
+  // gaps of iteration t (they carry nothing else), so that the SALU work sits under MFMAs.
+  u32x4 rk[kIT], rv[kIT], rk5 = {0u, 0u, 0u, 0u}, rv5 = {0u, 0u, 0u, 0u};
+  const int64_t kstep = (int64_t)kKBlk * a.k_sl * 2, vstep = (int64_t)kKBlk * a.v_sl * 2;
+  const char* kp = kbase + (kIT + 1) * kstep;
+  const char* vp = vbase + kIT * vstep;
+  int rows_k = Lk - (kIT + 1) * kKBlk, rows_v = Lk - kIT * kKBlk;
+  auto dma_next = [&](auto CC) __attribute__((always_inline)) {
+    constexpr int c = decltype(CC)::value;
+    if constexpr (c == 0) {
+#pragma unroll
+      for (int i = 0; i < kIT; ++i) rk[i] = tile_rsrc(kp + i * kstep, a.k_sl, min(rows_k - i * kKBlk, kKBlk));
+      kp += kIT * kstep;
+      rows_k -= kIT * kKBlk;
+    } else if constexpr (c == 1) {
+#pragma unroll
+      for (int i = 0; i < kIT; ++i) rv[i] = tile_rsrc(vp + i * vstep, a.v_sl, min(rows_v - i * kKBlk, kKBlk));
+      vp += kIT * vstep;
+      rows_v -= kIT * kKBlk;
+    } else if constexpr (kIT == 2) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        rk5[e] = img5 ? rk[kIT - 1][e] : rk[0][e];
+        rv5[e] = img5 ? rv[kIT - 1][e] : rv[0][e];
+      }
+    }
+  };
+  if constexpr (!kWqHeadRsrc) static_for<3>(dma_next);
+  constexpr int kNextAt = (2 * kIT - 1) * wq_stage(kNQ) + wq_stage(kNQ) - 3;  // the iteration slot of dma_next's step 0
+  static_assert(!wq_read_gap(kNQ, wq_stage(kNQ) - 3) && !wq_read_gap(kNQ, wq_stage(kNQ) - 2) &&
+                    !wq_read_gap(kNQ, wq_stage(kNQ) - 1) && wq_sm_op(kNQ, wq_stage(kNQ) - 3) < 0,
+                "a stage's last three gaps carry no read and no softmax instruction");
+
+  // One iteration t: the half stages st = 0 .. 2 kIT - 1, hs = st & 1, on image st >> 1 of the iteration's K and V
+  // buffers. Stage st's row sums and P.V read P[hs] and the V image's key step hs; its Q K^T reads the K image's key
+  // blocks 2 hs, 2 hs + 1 and writes S[hs]; its softmax reads S[1 - hs] and writes P[1 - hs]. FULL: the loop's
+  // iteration; else the prologue (two stages on K(0): no P.V, no first softmax, no DMA).
   auto body = [&](auto FULLC, int t) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(FULLC)::value;
-    constexpr int NF = FULL ? 32 : 16;  // live fragments, in order
+    constexpr int NST = FULL ? 2 * kIT : 2;  // half stages
+    constexpr int NF = FULL ? 16 * NST : 16;  // live fragments, in order
     constexpr auto frag_of = [](int n) constexpr { return FULL ? n : (n < 8 ? 8 + n : 16 + n); };
     constexpr auto seq_of = [](int F) constexpr { return FULL ? F : (F < 16 ? F - 8 : F - 16); };
     constexpr auto nreads = [](int F) constexpr { return F % 16 < 8 ? 2 : 1; };
-    k_cur = k_rd_lds + (((t + 1) & 1) ? (unsigned)KB1 : 0u);
-    v_cur = v_rd_lds + ((t & 1) ? (unsigned)kVBuf16 : 0u);
-    u32x4 rk = {0u, 0u, 0u, 0u}, rv = {0u, 0u, 0u, 0u};
-    unsigned dst_k = 0, dst_v = 0;
+    // the first key of the scores stage 0's softmax works on (stage st's: + 32 st)
+    const int key_sm = FULL ? 64 * kIT * t + 32 : -32;
+    unsigned dst_k = 0, dst_v = 0, dst_k5 = 0, dst_v5 = 0;
     if constexpr (FULL) {
-      mask_keys(std::integral_constant<int, 1>{}, 64 * t + 32);
-      rk = k_rsrc(t + 2);  // past the last tile: an empty range, the pieces land as zeros
-      rv = v_rsrc(t + 1);
-      dst_k = lds_wave + ((t & 1) ? (unsigned)KB1 : 0u);
-      dst_v = lds_wave + (unsigned)VB0 + (((t + 1) & 1) ? (unsigned)kVBuf16 : 0u);
+      k_cur = k_rd_lds + (((t + kPar) & 1) ? (unsigned)kBuf : 0u);
+      v_cur = v_rd_lds + ((t & 1) ? (unsigned)kBuf : 0u);
+      mask_keys(std::integral_constant<int, 1>{}, key_sm);
+      if constexpr (kWqHeadRsrc) {
+#pragma unroll
+        for (int i = 0; i < kIT; ++i) {
+          rk[i] = k_rsrc(kIT * (t + 1) + 1 + i);
+          rv[i] = v_rsrc(kIT * (t + 1) + i);
+        }
+        if constexpr (kIT == 2) dma_next(std::integral_constant<int, 2>{});
+      }
+      // the next iteration's tiles go into the two buffers the previous iteration read
+      const unsigned at_k = ((t + 1 + kPar) & 1) ? (unsigned)kBuf : 0u;
+      const unsigned at_v = (unsigned)VB0 + (((t + 1) & 1) ? (unsigned)kBuf : 0u);
+      dst_k = lds_wave + at_k;
+      dst_v = lds_wave + at_v;
+      if constexpr (kIT == 2) {  // pieces 16-17: of image 0 on waves 0-1, of image 1 on waves 2-3
+        dst_k5 = lds_wave5 + at_k;
+        dst_v5 = lds_wave5 + at_v;
+      }
+    } else {
+      k_cur = k_rd_lds + kK0At;  // K(0)
+      v_cur = v_rd_lds;          // (no P.V in the prologue)
     }
+    // DMA slot d of the iteration: its M0, then (one gap later) its load
+    auto dma_m0 = [&](auto DC) __attribute__((always_inline)) {
+      constexpr int d = decltype(DC)::value, i = d % (kND / 2);
+      constexpr bool isk = d < kND / 2;
+      (void)dst_k;
+      (void)dst_v;
+      (void)dst_k5;
+      (void)dst_v5;
+      if constexpr (kIT == 1) {
+        if (i < 4 || wave < 2) set_m0(isk ? dst_k : dst_v, std::integral_constant<int, 4096 * i>{});
+      } else if constexpr (i < 8) {
+        set_m0(isk ? dst_k : dst_v, std::integral_constant<int, (i / 4) * kWqImg + 4096 * (i % 4)>{});
+      } else {
+        set_m0(isk ? dst_k5 : dst_v5, std::integral_constant<int, 16384>{});
+      }
+    };
+    auto dma_ld = [&](auto DC) __attribute__((always_inline)) {
+      constexpr int d = decltype(DC)::value, i = d % (kND / 2);
+      constexpr bool isk = d < kND / 2;
+      (void)rk;
+      (void)rv;
+      (void)rk5;
+      (void)rv5;
+      if constexpr (kIT == 1) {
+        if (i < 4 || wave < 2) dma_load(isk ? rk[0] : rv[0], isk ? dk[i] : dv[i]);
+      } else if constexpr (i < 8) {
+        dma_load(isk ? rk[i / 4] : rv[i / 4], isk ? dk[i % 4] : dv[i % 4]);
+      } else {
+        dma_load(isk ? rk5 : rv5, isk ? dk[4] : dv[4]);
+      }
+    };
     static_for<kAheadWq>([&](auto IC) __attribute__((always_inline)) {
       constexpr int n = decltype(IC)::value;
       issue(std::integral_constant<int, frag_of(n)>{}, std::integral_constant<int, n % kR>{});
     });
     __builtin_amdgcn_sched_barrier(0);
-    static_for<2 * kNS>([&](auto MC) __attribute__((always_inline)) {
+    static_for<NST * kNS>([&](auto MC) __attribute__((always_inline)) {
       constexpr int M = decltype(MC)::value;
-      constexpr int st = M / kNS, m = M % kNS;
+      constexpr int st = M / kNS, m = M % kNS, hs = st & 1;
       constexpr int f = wq_frag(kNQ, m), qb = wq_qb(kNQ, m);
       constexpr int F = 16 * st + (f < 0 ? 0 : f);
       constexpr bool has_mfma = f >= 8 || FULL;
-      constexpr bool has_sm = st == 1 || FULL;
+      constexpr bool has_sm = st >= 1 || FULL;
       (void)S;  // (asm operands, named: clang's implicit capture into a generic lambda misses them otherwise)
       (void)ex;
       (void)pk;
@@ -393,13 +563,9 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
       (void)minit;
       (void)qa;
       (void)ring;
-      (void)rk;
-      (void)rv;
-      (void)dst_k;
-      (void)dst_v;
-      if constexpr (m == 0 && st == 1) {
+      if constexpr (m == 0 && st >= 1) {
         if constexpr (!FULL) asm volatile("s_nop 15" ::: "memory");  // no MFMA ahead of the softmax's first S reads
-        mask_keys(std::integral_constant<int, 0>{}, 64 * (t + 1));
+        mask_keys(std::integral_constant<int, 1 - hs>{}, key_sm + 32 * st);
         __builtin_amdgcn_sched_barrier(0);
       }
       if constexpr (has_mfma) {
@@ -414,28 +580,28 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
           asm volatile("s_waitcnt lgkmcnt(%0)" ::"i"(pending), "v"(ring[n % kR]) : "memory");
         }
         if constexpr (f < 0) {  // row sums: all-ones x P^T
-          asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+a"(lacc[qb]) : "a"(ones8), "v"(P[st][qb]));
+          asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+a"(lacc[qb]) : "a"(ones8), "v"(P[hs][qb]));
         } else if constexpr (f < 8) {  // O^T[db] += V^T(db, key step st) P^T
-          asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+a"(oacc[f][qb]) : "v"(ring[seq_of(F) % kR]), "v"(P[st][qb]));
+          asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+a"(oacc[f][qb]) : "v"(ring[seq_of(F) % kR]), "v"(P[hs][qb]));
         } else {  // S^T[kbl] (+)= K(kbl, s) Q^T(s)
           constexpr int kbl = (f - 8) & 1, s = (f - 8) >> 1;
           constexpr int ri = seq_of(F) % kR;
           if constexpr (qb < kQA) {
             if constexpr (s == 0 && kInit)
               asm volatile(WQ_MFMA "%0, %1, %2, %3"
-                           : "=&v"(S[st][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]), "v"(minit[qb]));
+                           : "=&v"(S[hs][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]), "v"(minit[qb]));
             else if constexpr (s == 0)
-              asm volatile(WQ_MFMA "%0, %1, %2, 0" : "=&v"(S[st][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]));
+              asm volatile(WQ_MFMA "%0, %1, %2, 0" : "=&v"(S[hs][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]));
             else
-              asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+v"(S[st][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]));
+              asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+v"(S[hs][kbl][qb]) : "v"(ring[ri]), "a"(qa[qb][s]));
           } else {
             if constexpr (s == 0 && kInit)
               asm volatile(WQ_MFMA "%0, %1, %2, %3"
-                           : "=&v"(S[st][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]), "v"(minit[qb]));
+                           : "=&v"(S[hs][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]), "v"(minit[qb]));
             else if constexpr (s == 0)
-              asm volatile(WQ_MFMA "%0, %1, %2, 0" : "=&v"(S[st][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]));
+              asm volatile(WQ_MFMA "%0, %1, %2, 0" : "=&v"(S[hs][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]));
             else
-              asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+v"(S[st][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]));
+              asm volatile(WQ_MFMA "%0, %1, %2, %0" : "+v"(S[hs][kbl][qb]) : "v"(ring[ri]), "v"(qa[qb][s]));
           }
         }
       }
@@ -446,15 +612,11 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
         if constexpr (n < NF) issue(std::integral_constant<int, frag_of(n)>{}, std::integral_constant<int, n % kR>{});
       }
       if constexpr (FULL) {
-        constexpr int dm = wq_m0_at(kNQ, M), dl = wq_dma_at(kNQ, M);
-        if constexpr (dm >= 0) {  // M0 of piece dm (j = dm % 5 of K(t + 2), then of V(t + 1))
-          constexpr int j = dm % 5;
-          if (j < 4 || wave < 2) set_m0(dm < 5 ? dst_k : dst_v, std::integral_constant<int, 4096 * j>{});
-        }
-        if constexpr (dl >= 0) {
-          constexpr int j = dl % 5;
-          if (j < 4 || wave < 2) dma_load(dl < 5 ? rk : rv, dl < 5 ? dk[j] : dv[j]);
-        }
+        constexpr int dm = wq_m0_at(kNQ, kIT, M), dl = wq_dma_at(kNQ, kIT, M);
+        if constexpr (dm >= 0) dma_m0(std::integral_constant<int, dm>{});
+        if constexpr (dl >= 0) dma_ld(std::integral_constant<int, dl>{});
+        if constexpr (!kWqHeadRsrc && M >= kNextAt && M < kNextAt + 3)  // (this iteration's loads are long issued)
+          dma_next(std::integral_constant<int, M - kNextAt>{});
       }
       if constexpr (has_sm) {
         if constexpr (!has_mfma) asm volatile("s_nop 1" ::: "memory");  // trans -> VALU use without an MFMA between
@@ -463,13 +625,13 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
           constexpr int q = op / 12, r = op % 12, pair = r / 3, w = r % 3;
           if constexpr (w < 2) {
             constexpr int j = 2 * pair + w;
-            asm volatile("v_exp_f32 %0, %1" : "=v"(ex[w]) : "v"(S[1 - st][j >> 2][q][j & 3]));
+            asm volatile("v_exp_f32 %0, %1" : "=v"(ex[w]) : "v"(S[1 - hs][j >> 2][q][j & 3]));
           } else {
             // the bf16 pack as a compiler conversion (v_cvt_pk_bf16_f32), pinned to this gap by the asm statement that
             // uses it
             pk[pair] = __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{ex[0], ex[1]}, bf16x2v));
             asm volatile("" ::"v"(pk[pair]));
-            if constexpr (pair == 3) P[1 - st][q] = __builtin_bit_cast(bf16x8, u32x4{pk[0], pk[1], pk[2], pk[3]});
+            if constexpr (pair == 3) P[1 - hs][q] = __builtin_bit_cast(bf16x8, u32x4{pk[0], pk[1], pk[2], pk[3]});
           }
         }
       }
@@ -495,7 +657,8 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // K(0), K(1), V(0)
   __builtin_amdgcn_s_barrier();
   body(std::false_type{}, -1);
-  for (int t = 0; t < ntk; ++t) body(std::true_type{}, t);
+  const int nit = (ntk + kIT - 1) / kIT;  // an odd tile count ends in a half-full iteration: P = 0 on zero V rows
+  for (int t = 0; t < nit; ++t) body(std::true_type{}, t);
 
   // ---- epilogue: O^T[16 db + 4 g + i][16 qb + c] = oacc[db][qb][i]: row row_w + 16 qb + c ----
   asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");  // the last MFMAs' accumulator writes -> v_accvgpr_read

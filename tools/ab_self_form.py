@@ -24,8 +24,11 @@ def main():
     ap.add_argument("--pairs", type=int, default=6)
     ap.add_argument("--forms", default="320", help="comma-separated widths to set against form 0")
     ap.add_argument("--norm-weights", default="", help="lo,hi: q/k norm weights uniform in [lo, hi] (online max)")
+    ap.add_argument("--lib", default="", help="lab build of libcp25.so to load instead of the in-tree one")
     a = ap.parse_args()
     from cosmos_predict2 import _native as N
+    if a.lib:
+        N._LIB_PATH = os.path.abspath(a.lib)
     from cosmos_predict2.pipeline import DEFAULT_NEGATIVE_PROMPT, Video2WorldInference
 
     dev = torch.device("cuda:0")
@@ -80,7 +83,7 @@ def main():
     med = {f: float(np.median(v)) for f, v in t.items()}
     print(json.dumps({"ms_per_eval": {str(f): v for f, v in t.items()}, "median": {str(f): m for f, m in med.items()},
                       "over_form0": {str(f): med[f] / med[0] for f in widths},
-                      "form0_spread": (max(t[0]) - min(t[0])) / med[0],
+                      "form0_spread": (max(t[0]) - min(t[0])) / med[0], "lib": os.path.basename(a.lib) or "libcp25.so",
                       "norm_weights": a.norm_weights or "ones (init)", "kernels_forced": {str(f): k for f, k in kernels.items()},
                       "kernels_default": model.net.attention_kernels(state_t * (h // 16) * (w // 16))}))
 

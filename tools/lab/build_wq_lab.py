@@ -1,0 +1,43 @@
+"""Lab builds of libcp25.so whose attn_wide.hip is compiled with one of attn_fwd_wq's isolation switches, for same-box
+A/B runs against the product library (tools/bench_attn.py --ab-libs, tools/ab_self_form.py --lib); every other unit is
+the in-tree object, and the source is the product file, so a lab build cannot drift from the kernel it is compared with.
+
+  python tools/lab/build_wq_lab.py parent            # -DCP25_WQ_PARENT_LOOP: round 13's loop (64 keys per iteration)
+  python tools/lab/build_wq_lab.py k128_nopad        # the product's 128-key loop without the padding fetch
+  python tools/lab/build_wq_lab.py k128_nopad_gaps   # and with the tile descriptors made in the iteration's last gaps
+  python tools/lab/build_wq_lab.py <name> -DX ...    # any other combination
+Writes tools/lab/libcp25_wq_<name>.so (never libcp25.so).
+"""
+import glob
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+CSRC = os.path.join(ROOT, "cosmos-predict2.5_amd", "csrc")
+OBJ = os.path.join(ROOT, "cosmos-predict2.5_amd", "cosmos_predict2", "_lib", "obj")
+NAMED = {"parent": ["-DCP25_WQ_PARENT_LOOP"],
+         "k128_nopad": ["-DCP25_WQ_NO_PAD_FETCH"],                            # the product + no padding fetch
+         "k128_nopad_gaps": ["-DCP25_WQ_NO_PAD_FETCH", "-DCP25_WQ_GAP_RSRC"],  # + the descriptors made in gaps
+         "k64_nopad": ["-DCP25_WQ_ITER_TILES=1", "-DCP25_WQ_NO_PAD_FETCH"],   # the parent + no padding fetch
+         "k64_gaps": ["-DCP25_WQ_ITER_TILES=1", "-DCP25_WQ_GAP_RSRC"]}        # the parent + the descriptors made in gaps
+
+
+def main():
+    name, defs = sys.argv[1], sys.argv[2:]
+    defs = defs or NAMED[name]
+    subprocess.check_call(["make", "-s", "-C", CSRC, "-j8"])
+    obj = os.path.join(OBJ, f"attn_wide_lab_{name}.o")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17",
+                           "-fhip-fp32-correctly-rounded-divide-sqrt", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC,
+                           "-fno-honor-nans", "-fno-slp-vectorize", *defs, "-c", os.path.join(CSRC, "attn_wide.hip"),
+                           "-o", obj])
+    others = [o for o in sorted(glob.glob(os.path.join(OBJ, "*.o")))
+              if not os.path.basename(o).startswith("attn_wide")]
+    out = os.path.join(ROOT, "tools", "lab", f"libcp25_wq_{name}.so")
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out, obj, *others])
+    print(out, " ".join(defs))
+
+
+if __name__ == "__main__":
+    main()
