@@ -131,6 +131,7 @@ SIGNATURES = {
     "cp25_kv_put": [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _I64, _I, _I64, _I64, _P],
     "cp25_stream_patchify_ld": [_P, _F, _F, _P, _P, _I64, _I64, _P],
     "cp25_stream_x0_step": [_P, _P, _P, _P, _F, _F, _F, _F, _D, _I, _I64, _P],
+    "cp25_stream_latent_clip": [_P, _P, _P, _P, _I, _I, _I, _P],
     "cp25_unipc_step": [_P, _P, _P, _P, _P, _I64, ctypes.POINTER(UniPCParams), _P],
     "cp25_conv3d": [ctypes.POINTER(ctypes.c_void_p), _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                     _I, _I, _I, _I, _I, _I, _P],
@@ -1226,6 +1227,28 @@ def stream_x0_step(xs: torch.Tensor, net: torch.Tensor, noise: Optional[torch.Te
                                                           float(c_out), float(cos_next), float(sin_next),
                                                           float(sigma_data), int(bool(last)), n_tok,
                                                           _stream(xs.device)))
+    return out
+
+
+def stream_latent_clip(rows: torch.Tensor, inv_std: torch.Tensor, mean: torch.Tensor, Hp: int, Wp: int,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """cp25_stream_latent_clip: one frame of the batched streaming state, rows [Hp * Wp, B, 64] bf16 (token-major, feature
+    (p1 * 2 + p2) * 16 + c) -> the VAE decoder's un-normalised channels-last input of that frame, [B, 2 Hp, 2 Wp, 16]
+    bf16 = bf16(bf16(x / inv_std[c]) + mean[c]); inv_std, mean: the [16] bf16 tensors WanVAE holds."""
+    lib = load_library()
+    if rows.dim() != 3 or rows.shape[0] != Hp * Wp or rows.shape[2] != 64 or rows.dtype != torch.bfloat16 \
+            or not rows.is_contiguous():
+        raise ValueError(f"rows must be contiguous bf16 [{Hp * Wp}, B, 64], got {rows.dtype} {tuple(rows.shape)}")
+    B = rows.shape[1]
+    for name, t in (("inv_std", inv_std), ("mean", mean)):
+        if t.dtype != torch.bfloat16 or t.numel() != 16 or not t.is_contiguous() or t.device != rows.device:
+            raise ValueError(f"{name} must be 16 contiguous bf16 values on {rows.device}")
+    if out is None:
+        out = torch.empty((B, 2 * Hp, 2 * Wp, 16), dtype=torch.bfloat16, device=rows.device)
+    elif out.dtype != torch.bfloat16 or tuple(out.shape) != (B, 2 * Hp, 2 * Wp, 16) or not out.is_contiguous():
+        raise ValueError(f"out must be contiguous bf16 {(B, 2 * Hp, 2 * Wp, 16)}")
+    _check("cp25_stream_latent_clip", lib.cp25_stream_latent_clip(_ptr(rows), _ptr(inv_std), _ptr(mean), _ptr(out),
+                                                                  int(B), int(Hp), int(Wp), _stream(rows.device)))
     return out
 
 

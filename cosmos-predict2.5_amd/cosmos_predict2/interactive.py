@@ -7,6 +7,9 @@ T = 4 latent frames one at a time over a K/V cache (model.StreamingRun, a few st
 them and contributes the 12 frames after the conditioning one. The noise seed is seed + chunk and the cache is rebuilt per
 chunk.
 
+Closed-loop use (ActionSession, `open_session`): the same chunk rules driven one latent frame at a time: 4 actions in,
+their 4 decoded frames out, so that a policy can pick its next actions from the frames it has just seen.
+
 The text embedding is an input tensor: the reference loads an empty-string embedding file (:130-148).
 Differences: the input frame is resized by this build's resize_input, not mediapy's; the frame arrives
 as an array or an image path, not as a video file whose frame 0 is read.
@@ -19,7 +22,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from .model import StreamingBatchRun, StreamingRun, session_seeds
+from .model import MAX_STREAM_BATCH, StreamingBatchRun, StreamingRun, session_seeds, upload_async
 from .pipeline import _IMAGE_EXTENSIONS, Video2WorldInference, resize_input
 
 MODEL_NAME = "2B/robot/action-cond/streaming"
@@ -48,6 +51,132 @@ def check_equal_frames(shapes: Sequence[Tuple[int, ...]]) -> Tuple[int, ...]:
         raise ValueError(f"the sessions' conditioning frames differ in size after the resize: {[tuple(s) for s in shapes]} "
                          "(pass resolution_hw)")
     return tuple(shapes[0])
+
+
+def session_step_plan(k: int, frames_per_chunk: int = CHUNK_ACTIONS // 4) -> Tuple[int, int, bool]:
+    """Step k (0, 1, ...) of a closed-loop session -> (chunk, latent frame within the chunk, opens a chunk). A chunk is
+    a conditioning frame (latent frame 0) plus frames_per_chunk generated latent frames, one per step; the step that
+    generates frame 1 opens the chunk (conditioning frame, encode, fresh cache, prefill) first."""
+    k, n = int(k), int(frames_per_chunk)
+    if k < 0 or n < 1:
+        raise ValueError(f"step {k} of chunks of {n} generated frames")
+    return k // n, 1 + k % n, k % n == 0
+
+
+def check_step_actions(actions, B: int, per: int, action_dim: int) -> torch.Tensor:
+    """One step's actions [B, per, action_dim] (numpy or tensor) of B sessions as a float tensor, or ValueError."""
+    if actions is None:
+        raise ValueError(f"a step takes the actions [{B}, {per}, {action_dim}] of its latent frame, got None")
+    a = actions if isinstance(actions, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(actions)))
+    if a.dim() != 3 or tuple(a.shape) != (B, per, action_dim):
+        raise ValueError(f"a step's actions must be [{B}, {per}, {action_dim}] ({per} actions per latent frame for "
+                         f"{B} sessions), got {tuple(a.shape)}")
+    return a.float()
+
+
+class ActionSession:
+    """B closed-loop sessions of the streaming student in lock-step: step(actions) takes one latent frame's 4 actions per
+    session and returns that frame's 4 decoded pixel frames. The chunk rules are stream_action_chunks_batch's, applied
+    as the steps arrive (session_step_plan): the step that opens a chunk builds the conditioning frame (the input frame,
+    then the last decoded frame re-quantised to uint8), encodes it, builds a StreamingBatchRun(actions=None) with a
+    fresh cache and the seeds seed_b + chunk_b, runs the prefill and pushes latent frame 0 into a fresh DecodeStream
+    (whose one pixel frame is dropped); every step then runs next_frame(action), hands the new frame's state rows to
+    the decoder (cp25_stream_latent_clip) and pushes them. Fed the same actions, the steps' frames are the chunk entry
+    points' frames bit for bit. Made by ActionStreamingInference.open_session."""
+
+    def __init__(self, inf: "ActionStreamingInference", first_frames, resolution_hw=None, num_steps: int = 4, seed=1,
+                 cache_frame_size: int = -1, output: str = "float"):
+        if output not in ("float", "u8"):
+            raise ValueError(f"output must be 'float' or 'u8', got {output!r}")
+        model = inf.pipe.model
+        ncfg = model.net_cfg
+        first_frames = list(first_frames)
+        B = len(first_frames)
+        if not 1 <= B <= MAX_STREAM_BATCH:
+            raise ValueError(f"a batch of {B} sessions: 1 .. {MAX_STREAM_BATCH} run in one forward")
+        seeds = session_seeds(seed, B)
+        if ncfg.action_per_latent_frame != 4:
+            raise ValueError("the chunk loop is written for 4 actions per latent frame (12 actions -> 3 latent frames)")
+        K = len(model.config.selected_sampling_time)
+        self.inf, self.B, self.output = inf, B, output
+        self.n_steps = max(1, min(int(num_steps), K))
+        self.cache_frame_size = cache_frame_size
+        frames = [inf._first_frame(f, resolution_hw) for f in first_frames]
+        _, self.H, self.W = check_equal_frames([tuple(f.shape) for f in frames])
+        frame = torch.stack(frames, 0)  # [B, 3, H, W] uint8
+        self.first_frames = frame.float()[:, :, None] / 128 - 1
+        self.on_device = inf.pipe.pixel_path == "device"
+        self._frame = frame.to(inf.pipe.device) if self.on_device else frame  # the next chunk's conditioning frames
+        self._seeds = seeds
+        self._chunk = [0] * B  # per session: chunks opened since its (re)start
+        self._T_lat = model.tokenizer.get_latent_num_frames(1 + CHUNK_ACTIONS)
+        self._run: Optional[StreamingBatchRun] = None
+        self._dec = None
+        self.steps_done = 0
+
+    @property
+    def at_chunk_start(self) -> bool:
+        """The next step opens a chunk (conditioning frame, fresh cache): where replace() is legal."""
+        return session_step_plan(self.steps_done, self._T_lat - 1)[2]
+
+    def replace(self, b: int, frame, seed: Optional[int] = None) -> None:
+        """Restart session b (the episode reset of a batched policy evaluation): its next chunk conditions on `frame`
+        (an array or image path, brought to the sessions' resolution) and counts as its chunk 0, with `seed` as its seed
+        if one is given. The other sessions continue. Only at a chunk start, where every session's cache is rebuilt."""
+        if not self.at_chunk_start:
+            raise RuntimeError("replace() is legal only at a chunk start (at_chunk_start): inside a chunk the sessions "
+                               "share one cache position")
+        if not 0 <= int(b) < self.B:
+            raise ValueError(f"session {b} of {self.B}")
+        t = self.inf._first_frame(frame, (self.H, self.W))
+        self._frame[int(b)] = t.to(self._frame.device)
+        self._chunk[int(b)] = 0
+        if seed is not None:
+            self._seeds[int(b)] = int(seed)
+
+    def _open_chunk(self) -> None:
+        inf = self.inf
+        model, B = inf.pipe.model, self.B
+        gt = model.encode_conditioning(self._frame[:, :, None], 1, self._T_lat)  # [B, C, T_lat, h, w]
+        if inf._ctx is None:
+            inf._ctx = model.net.prepare_context(inf.text_embeddings)
+        if inf._ctx_batch is None or inf._ctx_batch.B != B:
+            inf._ctx_batch = StreamingBatchRun.batch_context(model, inf._ctx, B)
+        seeds = [s + c for s, c in zip(self._seeds, self._chunk)]
+        self._run = StreamingBatchRun(model, gt, inf._ctx_batch, None, seed=seeds, n_steps=self.n_steps,
+                                      cache_frame_size=self.cache_frame_size)  # a fresh cache per chunk
+        self._run.next_frame()  # the prefill
+        self._dec = model.tokenizer.decode_stream(B)
+        geo = self._run.geo
+        self._dec.push_rows(self._run.frame_rows(0), geo.Hp, geo.Wp)  # the conditioning frame's pixel frame: dropped
+        self._chunk = [c + 1 for c in self._chunk]
+
+    @torch.no_grad()
+    def step(self, actions) -> torch.Tensor:
+        """actions [B, 4, action_dim] (numpy or tensor) -> the 4 frames they generate: [B, 3, 4, H, W] fp32 in [-1, 1]
+        on the host (output="float", a piece of stream_action_chunks_batch) or [B, 4, H, W, 3] uint8 on the device
+        (output="u8", decode_u8's quantisation; with pixel_path="device" no pixel leaves the device and the step does
+        not wait for it)."""
+        pipe = self.inf.pipe
+        ncfg = pipe.model.net_cfg
+        a = check_step_actions(actions, self.B, ncfg.action_per_latent_frame, ncfg.action_dim)
+        a = upload_async(a, pipe.device).to(torch.bfloat16)  # host actions: no wait for the device's earlier work
+        if self.at_chunk_start:
+            self._open_chunk()
+        run, B = self._run, self.B
+        f = run.next_frame(a)
+        clips = self._dec.push_rows(run.frame_rows(f), run.geo.Hp, run.geo.Wp)  # [B * 4, H, W, 3] bf16
+        per_clip = clips.unflatten(0, (B, -1))
+        self.steps_done += 1
+        if self.at_chunk_start:  # the chunk's last frame
+            # the next chunk's conditioning frames, re-quantised in the video's bf16 as the chunk loop does
+            video = per_clip[:, -1:].permute(0, 4, 1, 2, 3).clip(min=-1, max=1)  # [B, 3, 1, H, W]
+            frame = ((1.0 + video[:, :, -1]) / 2 * 255.0).to(torch.uint8)
+            self._frame = frame if self.on_device else frame.cpu()
+        if self.output == "u8":
+            u8 = pipe.model.tokenizer.model._clips_u8(clips, B, "THWC")
+            return u8 if B > 1 else u8[None]
+        return per_clip.permute(0, 4, 1, 2, 3).contiguous().clip(min=-1, max=1).float().cpu()
 
 
 class ActionStreamingInference:
@@ -207,3 +336,12 @@ class ActionStreamingInference:
         first_frames[b], actions_np[b] and seed_b."""
         return torch.cat(list(self.stream_action_chunks_batch(first_frames, actions_np, resolution_hw, num_steps, seed,
                                                               cache_frame_size)), dim=2)
+
+    # ------------------------------------------------------------------ closed loop
+    def open_session(self, first_frames, resolution_hw: Optional[Tuple[int, int]] = None, num_steps: int = 4, seed=1,
+                     cache_frame_size: int = -1, output: str = "float") -> ActionSession:
+        """B closed-loop sessions (ActionSession) from B conditioning frames (arrays or image paths, B = 1 .. 16):
+        `sess.first_frames` is the first piece of stream_action_chunks_batch, `sess.step(actions [B, 4, action_dim])`
+        returns the 4 frames those actions generate, and `sess.replace(b, frame, seed)` restarts one session at a chunk
+        start. Fed the actions of generate_action_streaming_batch, the steps reproduce its video bit for bit."""
+        return ActionSession(self, first_frames, resolution_hw, num_steps, seed, cache_frame_size, output)

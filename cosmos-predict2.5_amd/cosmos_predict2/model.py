@@ -44,6 +44,16 @@ def arch_invariant_rand(shape, dtype, device, seed: Optional[int] = None) -> tor
     return torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(dtype=dtype, device=device)
 
 
+def upload_async(t: torch.Tensor, device) -> torch.Tensor:
+    """A host tensor on `device`, unchanged in dtype and value, without waiting for the device's earlier work: through
+    pinned memory and a stream-ordered copy (a plain .to(device) of pageable memory synchronises the stream first)."""
+    device = torch.device(device)
+    if t.is_cuda or device.type != "cuda":
+        return t.to(device)
+    pinned = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+    return pinned.copy_(t).to(device, non_blocking=True)
+
+
 def to_patch_layout(x_C_T_H_W: torch.Tensor) -> torch.Tensor:
     """[C=16, T, H, W] -> [T*(H/2)*(W/2), 64] with feature (p1*2 + p2)*16 + c."""
     C, T, H, W = x_C_T_H_W.shape
@@ -654,10 +664,12 @@ class StreamingRun:
     the per-evaluation scalars are a few bf16 values made on the host (trigflow.stream_scaling / stream_renoise).
     The condition mask is all zeros in this loop (:514-516, :558-560), so t_cond never shows; the arithmetic that would
     apply it is kept (stream_scaling).
+    actions=None builds a closed-loop run: next_frame(action) then takes each generated frame's [1, per, dim] actions
+    when the frame is run, and nothing else changes (a frame never reads a later frame's actions).
     net_fn(rows [hw, 1, 72] bf16, t_B_1 [1, 1] fp32, geo, frame_idx, action [1, per, dim] | None, store) -> [hw, 1, 64]
     fp32 replaces forward_frame (tests only)."""
 
-    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt: torch.Tensor, ctx, actions: torch.Tensor, *,
+    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt: torch.Tensor, ctx, actions: Optional[torch.Tensor], *,
                  seed: int = 0, n_steps: int = 4, cache_frame_size: Optional[int] = None, net_fn=None,
                  init_noise: Optional[torch.Tensor] = None):
         cfg, ncfg, dev = model.config, model.net_cfg, model.device
@@ -668,10 +680,12 @@ class StreamingRun:
             raise ValueError(f"gt must be the [1, C, T, H, W] conditioning latent, got {tuple(gt.shape)}")
         _, C, T, H, W = gt.shape
         per = ncfg.action_per_latent_frame
-        if not per or actions.dim() != 3 or actions.shape[1] != (T - 1) * per or actions.shape[2] != ncfg.action_dim:
+        if not per or (actions is not None and (actions.dim() != 3 or actions.shape[1] != (T - 1) * per
+                                                or actions.shape[2] != ncfg.action_dim)):
             raise ValueError(f"actions must be [1, {(T - 1) * max(per, 1)}, {ncfg.action_dim}] for {T} latent frames "
-                             f"of a per-latent-frame action net, got {tuple(actions.shape)}")
+                             f"of a per-latent-frame action net, got {None if actions is None else tuple(actions.shape)}")
         self.model, self.net_fn, self.n_steps = model, net_fn, n_steps
+        self.B = 1
         self.state_shape = (C, T, H, W)
         self.geo = Geometry(T=T, Hp=H // 2, Wp=W // 2, tok0=0, n_tok=T * (H // 2) * (W // 2))
         hw = self.geo.hw
@@ -683,7 +697,8 @@ class StreamingRun:
         self.noise = to_patch_layout(init_noise[0].to(dev, bf)).view(T, hw, 64)  # init_noise.to(**tensor_kwargs)
         self.out = torch.zeros((T, hw, 64), dtype=bf, device=dev)  # output_latents, patch layout
         self.out[0] = to_patch_layout(gt[0, :, :1].to(dev, bf))
-        self.actions = actions.to(dev).view(actions.shape[0], T - 1, per, ncfg.action_dim)
+        self.actions = None if actions is None else actions.to(dev).view(actions.shape[0], T - 1, per, ncfg.action_dim)
+        self.action_shape = (1, per, ncfg.action_dim)
         F = cfg.cache_frame_size if cache_frame_size is None else cache_frame_size
         if F == 0 or F < -1:
             raise ValueError(f"cache_frame_size must be -1 (the whole clip) or positive, got {F}")
@@ -720,15 +735,16 @@ class StreamingRun:
                                             cache=self.cache, rows_k128=True)
 
     @torch.no_grad()
-    def next_frame(self) -> int:
-        """Run the next frame (the first call: the conditioning frame's prefill); returns its index."""
+    def next_frame(self, action: Optional[torch.Tensor] = None) -> int:
+        """Run the next frame (the first call: the conditioning frame's prefill); returns its index. A run built with
+        actions=None takes the frame's [1, per, dim] actions here, for every frame after the prefill."""
         if self.done:
             raise RuntimeError("every frame of the clip has been generated")
         f = self.frame
+        action = _frame_action(self, f, action)
         if f == 0:
             self._net(self.out[0], self.store_step, 0, None, True)
         else:
-            action = self.actions[:, f - 1]
             x = self.noise[f]
             for s in self.steps:
                 net_out = self._net(x, s, f, action, False)
@@ -744,6 +760,36 @@ class StreamingRun:
         """output_latents [1, C, T, H, W] bf16 (frames not yet generated are zero, as the reference initialises them)."""
         _, T, H, W = self.state_shape
         return from_patch_layout(self.out.view(-1, 64), T, H, W).unsqueeze(0)
+
+    def frame_rows(self, f: int) -> torch.Tensor:
+        """The [hw, 1, 64] bf16 state rows of frame f (the prefill's or a generated one), as cp25_stream_latent_clip
+        takes them: a view of the run's latents."""
+        return _frame_rows(self, f)
+
+
+def _frame_action(run, f: int, action: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """The actions of frame f of a streaming run: the slice of the run's action array, or, for a run built with
+    actions=None, the `action` [B, per, dim] given to next_frame (none for the prefill, f = 0)."""
+    if run.actions is not None:
+        if action is not None:
+            raise ValueError("this run was built with its action array; next_frame() takes no action")
+        return run.actions[:, f - 1] if f else None
+    if f == 0:
+        if action is not None:
+            raise ValueError("the prefill (the first next_frame) takes no action")
+        return None
+    if action is None:
+        raise ValueError(f"a run built with actions=None takes frame {f}'s actions {run.action_shape} in next_frame")
+    if not isinstance(action, torch.Tensor) or tuple(action.shape) != run.action_shape:
+        got = tuple(action.shape) if isinstance(action, torch.Tensor) else type(action).__name__
+        raise ValueError(f"frame {f}'s actions must be a {run.action_shape} tensor, got {got}")
+    return action.to(run.model.device)
+
+
+def _frame_rows(run, f: int) -> torch.Tensor:
+    if not 0 <= f < run.frame:
+        raise ValueError(f"frame {f} has not been run ({run.frame} of {run.geo.T} frames so far)")
+    return run.out[f].view(run.geo.hw, run.B, 64)
 
 
 MAX_STREAM_BATCH = 16
@@ -771,10 +817,12 @@ class StreamingBatchRun:
     [hw, B, 72] forward_frame takes. The text context's per-block K / V are made once for one entry and replicated B
     times (ContextCache of batch B). Session b computes what StreamingRun computes for its inputs; which launches keep
     its bits at B > 1 is in DESIGN.md §6e.
+    actions=None builds a closed-loop run: next_frame(action) then takes each generated frame's [B, per, dim] actions
+    when the frame is run (StreamingRun), and frame_rows(f) hands a finished frame to the decoder without a copy.
     net_fn(rows [hw, B, 72], t_B_1 [B, 1], geo, frame_idx, action [B, per, dim] | None, store) -> [hw, B, 64] fp32
     replaces forward_frame (tests only)."""
 
-    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt: torch.Tensor, ctx, actions: torch.Tensor, *,
+    def __init__(self, model: "Video2WorldModelRectifiedFlow", gt: torch.Tensor, ctx, actions: Optional[torch.Tensor], *,
                  seed=0, n_steps: int = 4, cache_frame_size: Optional[int] = None, net_fn=None,
                  init_noise: Optional[torch.Tensor] = None):
         cfg, ncfg, dev = model.config, model.net_cfg, model.device
@@ -787,17 +835,22 @@ class StreamingBatchRun:
         if not 1 <= B <= MAX_STREAM_BATCH:
             raise ValueError(f"a batch of {B} sessions: 1 .. {MAX_STREAM_BATCH} run in one forward")
         per = ncfg.action_per_latent_frame
-        if (not per or actions.dim() != 3 or actions.shape[0] != B or actions.shape[1] != (T - 1) * per
-                or actions.shape[2] != ncfg.action_dim):
+        if not per or (actions is not None and (actions.dim() != 3 or actions.shape[0] != B
+                                                or actions.shape[1] != (T - 1) * per
+                                                or actions.shape[2] != ncfg.action_dim)):
             raise ValueError(f"actions must be [{B}, {(T - 1) * max(per, 1)}, {ncfg.action_dim}] for {B} sessions of {T} "
-                             f"latent frames of a per-latent-frame action net, got {tuple(actions.shape)}")
+                             f"latent frames of a per-latent-frame action net, got "
+                             f"{None if actions is None else tuple(actions.shape)}")
         self.model, self.net_fn, self.n_steps, self.B = model, net_fn, n_steps, B
         self.state_shape = (C, T, H, W)
         self.geo = Geometry(T=T, Hp=H // 2, Wp=W // 2, tok0=0, n_tok=T * (H // 2) * (W // 2))
         hw = self.geo.hw
         bf = torch.bfloat16
         if init_noise is None:
-            noise = [arch_invariant_rand((1, C, T, H, W), torch.float32, dev, s)[0] for s in session_seeds(seed, B)]
+            # drawn on the host as arch_invariant_rand draws it, uploaded without a stream synchronise (a closed-loop
+            # session builds a run per chunk inside its step)
+            noise = [upload_async(arch_invariant_rand((1, C, T, H, W), torch.float32, "cpu", s)[0], dev)
+                     for s in session_seeds(seed, B)]
         elif tuple(init_noise.shape) != (B, C, T, H, W):
             raise ValueError(f"init_noise {tuple(init_noise.shape)} is not the state shape {(B, C, T, H, W)}")
         else:
@@ -806,7 +859,8 @@ class StreamingBatchRun:
         self.noise = torch.stack([to_patch_layout(n.to(dev, bf)).view(T, hw, 64) for n in noise], dim=2).contiguous()
         self.out = torch.zeros((T, hw, B, 64), dtype=bf, device=dev)
         self.out[0] = torch.stack([to_patch_layout(gt[b, :, :1].to(dev, bf)) for b in range(B)], dim=1)
-        self.actions = actions.to(dev).view(B, T - 1, per, ncfg.action_dim)
+        self.actions = None if actions is None else actions.to(dev).view(B, T - 1, per, ncfg.action_dim)
+        self.action_shape = (B, per, ncfg.action_dim)
         F = cfg.cache_frame_size if cache_frame_size is None else cache_frame_size
         if F == 0 or F < -1:
             raise ValueError(f"cache_frame_size must be -1 (the whole clip) or positive, got {F}")
@@ -820,7 +874,7 @@ class StreamingBatchRun:
         self.sigma_data = float(cfg.sigma_data)
 
         def t_rows(c_noise):  # one time for every session
-            return trigflow.net_timesteps(c_noise, ncfg.timestep_scale).to(dev).expand(B, 1).contiguous()
+            return upload_async(trigflow.net_timesteps(c_noise, ncfg.timestep_scale), dev).expand(B, 1).contiguous()
 
         self.steps = []
         for s in range(n_steps):
@@ -858,15 +912,16 @@ class StreamingBatchRun:
                                             cache=self.cache, rows_k128=True)
 
     @torch.no_grad()
-    def next_frame(self) -> int:
-        """Run every session's next frame (the first call: the conditioning frames' prefill); returns its index."""
+    def next_frame(self, action: Optional[torch.Tensor] = None) -> int:
+        """Run every session's next frame (the first call: the conditioning frames' prefill); returns its index. A run
+        built with actions=None takes the frame's [B, per, dim] actions here, for every frame after the prefill."""
         if self.done:
             raise RuntimeError("every frame of the clip has been generated")
         f, n = self.frame, self.geo.hw * self.B
+        action = _frame_action(self, f, action)
         if f == 0:
             self._net(self.out[0], self.store_step, 0, None, True)
         else:
-            action = self.actions[:, f - 1]
             noise = self.noise[f].view(n, 64)
             x = noise
             for s in self.steps:
@@ -883,3 +938,8 @@ class StreamingBatchRun:
         """output_latents [B, C, T, H, W] bf16 (frames not yet generated are zero)."""
         _, T, H, W = self.state_shape
         return torch.stack([from_patch_layout(self.out[:, :, b].reshape(-1, 64), T, H, W) for b in range(self.B)], 0)
+
+    def frame_rows(self, f: int) -> torch.Tensor:
+        """The [hw, B, 64] bf16 state rows of frame f (the prefill's or a generated one), as cp25_stream_latent_clip
+        takes them: a view of the run's latents."""
+        return _frame_rows(self, f)

@@ -27,7 +27,7 @@ end. Every output pixel is computed from the same inputs in the same order as th
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -538,24 +538,39 @@ class WanVAE:
         """latent -> uint8 video, [T, H, W, 3] ("THWC") or [1, 3, T, H, W] ("NCTHW"): decode's channels-last
         result quantised by cp25_clip_to_u8 (trunc(clamp((v + 1) / 2, 0, 1) * 255)), with no NCTHW or fp32 copy.
         B > 1 latents give [B, T, H, W, 3] or [B, 3, T, H, W], clip b as its own B = 1 call."""
-        from .pixels import clip_to_uint8
-
         if layout not in ("THWC", "NCTHW"):
             raise ValueError(f"layout must be 'THWC' or 'NCTHW', got {layout!r}")
-        B = z.shape[0]
-        clips = self._decode_clip(z)
+        return self._clips_u8(self._decode_clip(z), z.shape[0], layout)
+
+    @staticmethod
+    def _clips_u8(clips: torch.Tensor, B: int, layout: str) -> torch.Tensor:
+        """decode_u8's quantisation of the channels-last clips [B * t, H, W, 3] (clip-major)."""
+        from .pixels import clip_to_uint8
+
         if B == 1:
             return clip_to_uint8(clips, layout)
         outs = [clip_to_uint8(c, layout) for c in clips.unflatten(0, (B, -1))]
         return torch.stack(outs, 0) if layout == "THWC" else torch.cat(outs, 0)
+
+    def _unnormalised(self, z: torch.Tensor) -> torch.Tensor:
+        """latent [nb, 16, T, h, w] -> the decoder's channels-last clips [nb * T, h, w, 16] bf16, z / inv_std + mean."""
+        zl = z.to(self.device, BF16).permute(0, 2, 3, 4, 1).contiguous().flatten(0, 1)
+        return zl / self.inv_std + self.mean
+
+    def _conv2(self, zl: torch.Tensor, h: int, w: int) -> torch.Tensor:
+        """The decoder's 1x1x1 conv2 over every frame of the self._nb clips zl [nb * T, h, w, 16] (clip-major)."""
+        return self.convs["conv2"](_frames(zl), zl.shape[0], h, w, n_clips=self._nb)
+
+    def decode_stream(self, n_clips: int = 1) -> "DecodeStream":
+        """A decoder of n_clips clips in lock-step that takes one latent frame per push (DecodeStream)."""
+        return DecodeStream(self, n_clips)
 
     def _decode_clip(self, z: torch.Tensor) -> torch.Tensor:
         """latent [B, 16, T, h, w] -> channels-last video [B * Tp, H, W, 3] bf16, clip-major (bands gathered under CP)."""
         if z.dim() != 5 or z.shape[0] < 1:
             raise ValueError(f"decode takes a [B, 16, T, h, w] latent, got {tuple(z.shape)}")
         nb, C, T, h, w = z.shape
-        zl = z.to(self.device, BF16).permute(0, 2, 3, 4, 1).contiguous().flatten(0, 1)  # [nb * T, h, w, 16]
-        zl = zl / self.inv_std + self.mean
+        zl = self._unnormalised(z)
         group = self.cp_group
         r, n = cpx.cp_rank_world(group)
         if n > 1 and h % n == 0:
@@ -566,7 +581,7 @@ class WanVAE:
             h = h // n
         self._nb = nb
         try:
-            x = self.convs["conv2"](_frames(zl.contiguous()), nb * T, h, w, n_clips=nb)
+            x = self._conv2(zl.contiguous(), h, w)
             x5 = x.unflatten(0, (nb, T))
             cache = _FeatCache()
             outs = []
@@ -583,6 +598,76 @@ class WanVAE:
             self._band = None
             self._nb = 1
         return video
+
+
+class DecodeStream:
+    """WanVAE.decode one latent frame at a time: the decoder is causal and _decode_clip already runs it frame by frame
+    over a feature cache, so a stream that owns that cache between calls gives decode's frames as the latents arrive.
+    push(z) takes the next latent frame of the n_clips clips, z [B, 16, 1, h, w] (a normalised latent, as decode takes)
+    or [B, h, w, 16] bf16 channels-last and already un-normalised (cp25_stream_latent_clip's output), and returns the
+    decoder's frames of it, [B * t, H, W, 3] bf16 clip-major: t = 1 for the first push, 4 for every later one. The pushes
+    of the frames of z [B, 16, T, h, w] concatenated per clip are decode(z) bit for bit. The VAE's clip count is set per
+    push, so decode, encode and other streams of the same WanVAE may run between two pushes. One clip size per stream;
+    not under a context-parallel group (the banded decode gathers whole clips)."""
+
+    def __init__(self, vae: "WanVAE", n_clips: int = 1):
+        if int(n_clips) < 1:
+            raise ValueError(f"a decode stream takes at least one clip, got {n_clips}")
+        self.vae, self.n_clips = vae, int(n_clips)
+        self._check_cp()
+        self.cache = _FeatCache()
+        self.frames = 0  # latent frames pushed
+        self.hw: Optional[Tuple[int, int]] = None
+
+    def _check_cp(self) -> None:
+        if self.vae.cp_group is not None:
+            raise ValueError("decode_stream does not run under a context-parallel group (the banded decode takes a "
+                             "whole clip)")
+
+    @torch.no_grad()
+    def push(self, z: torch.Tensor) -> torch.Tensor:
+        vae, nb = self.vae, self.n_clips
+        self._check_cp()
+        if z.dim() == 5 and z.shape[0] == nb and z.shape[1] == vae.z_dim and z.shape[2] == 1:
+            zl = vae._unnormalised(z)
+        elif z.dim() == 4 and z.shape[0] == nb and z.shape[3] == vae.z_dim and z.dtype == BF16:
+            zl = z.to(vae.device)
+        else:
+            raise ValueError(f"push takes one latent frame of {nb} clips, [{nb}, {vae.z_dim}, 1, h, w] or un-normalised "
+                             f"bf16 [{nb}, h, w, {vae.z_dim}], got {z.dtype} {tuple(z.shape)}")
+        h, w = zl.shape[1:3]
+        if self.hw is None:
+            self.hw = (h, w)
+        elif self.hw != (h, w):
+            raise ValueError(f"this stream decodes {self.hw} latents, got {(h, w)}")
+        vae._nb = nb
+        try:
+            x = vae._conv2(zl.contiguous(), h, w)  # [nb, h, w, 16]
+            self.cache.idx = 0
+            o, _, _ = vae._decoder(x, self.cache, h, w)
+        finally:
+            vae._nb = 1
+        self.frames += 1
+        return o
+
+    def push_rows(self, rows: torch.Tensor, Hp: int, Wp: int) -> torch.Tensor:
+        """push of one frame of the streaming student's token-major state, rows [Hp * Wp, B, 64] bf16
+        (StreamingBatchRun.frame_rows): the rows go to the decoder's un-normalised frame in one kernel
+        (cp25_stream_latent_clip), with no NCTHW latent in between."""
+        if rows.dim() != 3 or rows.shape[1] != self.n_clips:
+            raise ValueError(f"rows must be [hw, {self.n_clips}, 64], got {tuple(rows.shape)}")
+        return self.push(N.stream_latent_clip(rows, self.vae.inv_std, self.vae.mean, Hp, Wp))
+
+    def push_video(self, z: torch.Tensor) -> torch.Tensor:
+        """push in decode's layout: [B, 3, t, H, W] bf16."""
+        return self.push(z).unflatten(0, (self.n_clips, -1)).permute(0, 4, 1, 2, 3).contiguous()
+
+    def push_u8(self, z: torch.Tensor, layout: str = "THWC") -> torch.Tensor:
+        """push quantised as decode_u8 does: [t, H, W, 3] / [1, 3, t, H, W] for one clip, [B, t, H, W, 3] /
+        [B, 3, t, H, W] for more."""
+        if layout not in ("THWC", "NCTHW"):
+            raise ValueError(f"layout must be 'THWC' or 'NCTHW', got {layout!r}")
+        return self.vae._clips_u8(self.push(z), self.n_clips, layout)
 
 
 class Wan2pt1VAEInterface:
@@ -613,6 +698,10 @@ class Wan2pt1VAEInterface:
         """latent -> uint8 device video [T, H, W, 3] ("THWC") or [1, 3, T, H, W] ("NCTHW"); [B, ...] latents with
         B > 1 give [B, T, H, W, 3] or [B, 3, T, H, W] (WanVAE.decode_u8)."""
         return self.model.decode_u8(latent, layout)
+
+    def decode_stream(self, n_clips: int = 1) -> DecodeStream:
+        """A decoder that takes one latent frame of n_clips clips per push (WanVAE.decode_stream)."""
+        return self.model.decode_stream(n_clips)
 
     def get_latent_num_frames(self, num_pixel_frames: int) -> int:
         return 1 + (num_pixel_frames - 1) // 4

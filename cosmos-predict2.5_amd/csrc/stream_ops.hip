@@ -8,6 +8,9 @@
 //                             forward_seq's mask channel, interactive/networks/dit_action_causal.py:625)
 //   cp25_stream_x0_step     : x0 = c_skip x + c_out net (:226), then x0 itself (last step) or the re-noising
 //                             cos(t_next) x0 / sigma_data + sin(t_next) noise (:442-444)
+//   cp25_stream_latent_clip : one generated frame of the token-major state -> the VAE decoder's channels-last input of
+//                             that frame, un-normalised (from_patch_layout + the permute and `zl / inv_std + mean` of
+//                             WanVAE._decode_clip; the reference's decode, tokenizers/wan2pt1.py:555-558)
 //
 // The student's arithmetic is bf16 op by op: every torch op of the reference is one operation on bf16 tensors, which
 // PyTorch's elementwise kernels evaluate in fp32 and round once to bf16 (DESIGN.md §6e has the operand-by-operand
@@ -134,6 +137,32 @@ __global__ void __launch_bounds__(256) stream_x0_step_kernel(const unsigned shor
   }
   *reinterpret_cast<u16x8*>(out + i * 8) = r;
 }
+// ---------------------------------------------------------------- state rows -> the decoder's un-normalised frame
+// One lane per 16-byte chunk of the row-major input: chunk id -> (row = tok * B + b, p = p1 * 2 + p2, channel half).
+// dst [B][2 Hp][2 Wp][16]: pixel (2 i + p1, 2 j + p2) of clip b, tok = i * Wp + j. Two bf16 ops per element: the IEEE
+// fp32 division by inv_std[c], then the addition of mean[c].
+__global__ void __launch_bounds__(256) stream_latent_clip_kernel(const unsigned short* __restrict__ xs,
+                                                                 const unsigned short* __restrict__ inv_std,
+                                                                 const unsigned short* __restrict__ mean,
+                                                                 unsigned short* __restrict__ dst, int B, int Hp, int Wp,
+                                                                 int64_t n_chunks) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_chunks) return;
+  const int64_t row = i >> 3;
+  const int c8 = (int)(i & 7);
+  const int p1 = c8 >> 2, p2 = (c8 >> 1) & 1, half = c8 & 1;
+  const int64_t tok = row / B;
+  const int b = (int)(row % B);
+  const int64_t ti = tok / Wp, tj = tok % Wp;
+  const u16x8 x = *reinterpret_cast<const u16x8*>(xs + i * 8);
+  const u16x8 is = *reinterpret_cast<const u16x8*>(inv_std + half * 8);
+  const u16x8 mu = *reinterpret_cast<const u16x8*>(mean + half * 8);
+  u16x8 r;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) r[k] = tbf(rtb(bf2f(x[k]) / bf2f(is[k])) + bf2f(mu[k]));
+  const int64_t pix = ((int64_t)b * (2 * Hp) + (2 * ti + p1)) * (2 * (int64_t)Wp) + (2 * tj + p2);
+  *reinterpret_cast<u16x8*>(dst + pix * 16 + half * 8) = r;
+}
 }  // namespace
 
 extern "C" int cp25_kv_put(const void* qkv, int64_t ld, int64_t k_col0, int64_t v_col0, int64_t D, void* k_cache,
@@ -180,6 +209,19 @@ extern "C" int cp25_stream_x0_step(const void* xs, const float* net, const void*
   hipLaunchKernelGGL(stream_x0_step_kernel, dim3((unsigned)cdiv(n_tok * 8, 256)), dim3(256), 0, stream,
                      (const unsigned short*)xs, net, (const unsigned short*)noise, (unsigned short*)out, c_skip, c_out,
                      cos_next, sin_next, inv_sd, last, n_tok * 8);
+  CP25_LAUNCH_CHECK();
+  return CP25_OK;
+}
+
+extern "C" int cp25_stream_latent_clip(const void* xs, const void* inv_std, const void* mean, void* dst, int B, int Hp,
+                                       int Wp, hipStream_t stream) {
+  if (!xs || !inv_std || !mean || !dst || B <= 0 || Hp <= 0 || Wp <= 0) return CP25_ERR_INVAL;
+  if (!aligned16({xs, inv_std, mean, dst})) return CP25_ERR_INVAL;
+  const int64_t n_chunks = (int64_t)Hp * Wp * B * 8;
+  if (cdiv(n_chunks, 256) > 0x7fffffff) return CP25_ERR_INVAL;
+  hipLaunchKernelGGL(stream_latent_clip_kernel, dim3((unsigned)cdiv(n_chunks, 256)), dim3(256), 0, stream,
+                     (const unsigned short*)xs, (const unsigned short*)inv_std, (const unsigned short*)mean,
+                     (unsigned short*)dst, B, Hp, Wp, n_chunks);
   CP25_LAUNCH_CHECK();
   return CP25_OK;
 }

@@ -547,6 +547,19 @@ int cp25_stream_x0_step(const void* xs, const float* net, const void* noise, voi
                         float cos_next, float sin_next, double sigma_data, int last, int64_t n_tok,
                         hipStream_t stream);
 
+/* One generated latent frame of the batched streaming state, xs [Hp * Wp * B, 64] bf16 (row = tok * B + b,
+ * tok = i * Wp + j, feature (p1 * 2 + p2) * 16 + c), into the VAE decoder's input of that frame, dst [B][2 Hp][2 Wp][16]
+ * bf16 channels-last, un-normalised:
+ *   dst[b][2 i + p1][2 j + p2][c] = bf16(float(bf16(float(x) / float(inv_std[c]))) + float(mean[c]))
+ * inv_std, mean: [16] bf16 device tensors (16-byte aligned, as xs and dst). The division is the IEEE-rounded fp32
+ * division of cp25_u8_to_clip; each (tok, b, p) is 32 contiguous bytes in and out, moved as 16-byte vectors. -22 for a
+ * misaligned pointer or a non-positive B, Hp or Wp.
+ * Replaces, per frame: the B from_patch_layout copies and their stack, then the decode's permute + .contiguous() and
+ * `zl / inv_std + mean` (the un-normalisation of WanVAE.decode, tokenizers/wan2pt1.py:555-558, on the frame
+ * generate_next_frame returns, interactive/models/action_video2world_self_forcing.py:383-447). */
+int cp25_stream_latent_clip(const void* xs, const void* inv_std, const void* mean, void* dst, int B, int Hp, int Wp,
+                            hipStream_t stream);
+
 /* ---------------------------------------------------------------- UniPC sampler update
  * Host-computed fp32 coefficients of one FlowUniPCMultistepScheduler.step. */
 typedef struct cp25_unipc_params {
