@@ -27,12 +27,16 @@
 // S(u) (per query block 8 v_exp_f32 and 4 bf16 packs: 12 kNQ instructions, placed by the compile-time gap plan below),
 // the operand reads two fragments ahead (a ring of three) and the LDS-DMA pieces.
 //
-// The LDS keeps attn_fwd_m16's image of a 64-key K or V tile (288-B rows); a buffer is TWO such images back to back,
-// two buffers each of K and V (147 456 B), and there is ONE buffer flip, DMA batch, vmcnt(0) drain and workgroup
-// barrier per 128 keys (round 17; round 13 had one per 64). Iteration t is the four half stages u = 4 t + 1 .. 4 t + 4:
+// The LDS image of a 64-key K or V tile is attn_wq_image.h's (round 18): plain 256-B rows, four to a 1-KiB DMA piece,
+// the pieces 1056 B apart, so that row r starts 32 (r & 7) bytes into the 256-B bank window as in attn_fwd_m16's
+// 288-B rows (the same conflict-free ds_read_b128 K reads and ds_read_b64_tr_b16 V reads, one base register each),
+// but a tile is 16 pieces instead of 18 and no DMA lane fetches padding: every wave moves four pieces of every image.
+// A buffer is TWO such images back to back, two buffers each of K and V (135 168 B), and there is ONE buffer flip,
+// DMA batch, vmcnt(0) drain and workgroup barrier per 128 keys (round 17; round 13 had one per 64). Iteration t is the
+// four half stages u = 4 t + 1 .. 4 t + 4:
 // stage st reads V(2 t + (st >> 1)) (key step st & 1) and K(2 t + 1 + (st >> 1)) (key blocks 2 (st & 1), + 1) and
 // nothing else, so K's buffers are cut one tile later than V's: iteration t reads the K buffer {K(2 t + 1), K(2 t + 2)}
-// and the V buffer {V(2 t), V(2 t + 1)}, and the 18 DMA pieces a wave moves (9 of K(2 t + 3), K(2 t + 4), 9 of
+// and the V buffer {V(2 t), V(2 t + 1)}, and the 16 DMA pieces a wave moves (8 of K(2 t + 3), K(2 t + 4), 8 of
 // V(2 t + 2), V(2 t + 3)) go to the two buffers the previous iteration read. Each wave drains its pieces (vmcnt(0))
 // before the closing barrier, which publishes them. The DMA is the bounds-checked buffer form: rows past the last key
 // read as zeros, so the ragged tile and the virtual tiles past it need no path of their own; scores of keys >= Lk
@@ -43,6 +47,7 @@
 // iterations. Its last Q K^T and softmax work on a virtual tile no one reads, and with an odd tile count its last two
 // stages on a virtual V tile too: P = 0 exactly on zero V rows, which adds +0 to O^T and to the row sums.
 #include "attn_common.h"
+#include "attn_wq_image.h"
 
 namespace cp25attn {
 namespace {
@@ -77,35 +82,46 @@ static_assert(wq_sm_count(5) == 60 && wq_sm_count(6) == 72, "every softmax instr
 // two, so the LDS holds two buffers of two 64-key images each for K and for V. -DCP25_WQ_PARENT_LOOP (tools/lab
 // only, never libcp25.so) rebuilds round 13's loop for A/B runs: one tile per iteration, the fifth DMA piece on
 // waves 0-1 alone.
-// Two further lab switches, each measured inside the run-to-run spread on its own and so not in the product
-// (profiles/r17/attn_k128/SUMMARY.md): -DCP25_WQ_NO_PAD_FETCH gives the lanes of the row padding an offset outside
-// every descriptor, so they fetch nothing; -DCP25_WQ_GAP_RSRC makes the tile descriptors by adds in the last three
-// gaps of the iteration before, under MFMAs, instead of at the head of the iteration behind the barrier.
+// -DCP25_WQ_PAD_IMAGE (lab only) keeps round 17's image for A/B runs: attn_fwd_m16's 64 rows of 288 B, 18 pieces a
+// tile, the padding lanes re-reading the tile's first 16 B, pieces 16-17 of the two images of a buffer on waves 0-1 and
+// 2-3 (the parent loop implies it).
+// -DCP25_WQ_HEAD_RSRC (lab only) computes the tile descriptors at the head of the iteration, behind the barrier, as
+// rounds 13 and 17 did; the product makes them by adds in the last gaps of the iteration before, under MFMAs (round
+// 18: shipped together with the image, profiles/r18/attn_image/SUMMARY.md). The parent loop implies it.
 #ifdef CP25_WQ_PARENT_LOOP
 #define CP25_WQ_ITER_TILES 1
-#undef CP25_WQ_NO_PAD_FETCH
-#undef CP25_WQ_GAP_RSRC
+#ifndef CP25_WQ_PAD_IMAGE
+#define CP25_WQ_PAD_IMAGE
+#endif
+#ifndef CP25_WQ_HEAD_RSRC
+#define CP25_WQ_HEAD_RSRC
+#endif
 #endif
 #ifndef CP25_WQ_ITER_TILES
 #define CP25_WQ_ITER_TILES 2
 #endif
 constexpr int wq_iter_tiles(int) { return CP25_WQ_ITER_TILES; }
-#ifdef CP25_WQ_NO_PAD_FETCH
-constexpr bool kWqPadFetch = false;
+#ifdef CP25_WQ_PAD_IMAGE
+constexpr bool kWqPad = true;
 #else
-constexpr bool kWqPadFetch = true;
+constexpr bool kWqPad = false;
 #endif
-#ifdef CP25_WQ_GAP_RSRC
-constexpr bool kWqHeadRsrc = false;
-#else
+#ifdef CP25_WQ_HEAD_RSRC
 constexpr bool kWqHeadRsrc = true;
+#else
+constexpr bool kWqHeadRsrc = false;
 #endif
-constexpr int kWqImg = kKBuf16;  // one 64-key image
 static_assert(kKBuf16 == kVBuf16, "K and V images of one size");
-// DMA slots of a wave per iteration: one tile, 5 K + 5 V pieces (the fifth on waves 0-1 only: 18 pieces a tile over
-// 4 waves); two tiles, 9 + 9: pieces 0-15 of both images on every wave, pieces 16-17 of image 0 on waves 0-1 and of
-// image 1 on waves 2-3
-constexpr int wq_dma_n(int it) { return it == 1 ? 10 : 18; }
+constexpr int kWqImg = kWqPad ? kKBuf16 : wqimg::kImage;  // one 64-key image
+// a wave's pieces j = 0..3 of an image: LDS byte kWqPieceAt wave + kWqPieceStep j of it
+constexpr int kWqPieceAt = kWqPad ? 1024 : wqimg::kPieceStride;
+constexpr int kWqPieceStep = 4 * kWqPieceAt;
+// lane offsets of a wave per operand: one per piece j, and the pad image's fifth (pieces 16-17)
+constexpr int kWqOffs = kWqPad ? 5 : 4;
+// DMA slots of a wave per iteration: 4 K + 4 V pieces per tile. The pad image: one tile, 5 K + 5 V pieces (the fifth
+// on waves 0-1 only: 18 pieces a tile over 4 waves); two tiles, 9 + 9: pieces 0-15 of both images on every wave, pieces
+// 16-17 of image 0 on waves 0-1 and of image 1 on waves 2-3
+constexpr int wq_dma_n(int it) { return !kWqPad ? 8 * it : it == 1 ? 10 : 18; }
 // DMA slot d (K first, then V) in the gap after iteration slot M, or -1: the read gaps of the iteration's first
 // wq_dma_n fragments; its M0 one gap earlier
 constexpr int wq_dma_at(int nq, int it, int M) {
@@ -115,8 +131,6 @@ constexpr int wq_dma_at(int nq, int it, int M) {
   return F < wq_dma_n(it) ? F : -1;
 }
 constexpr int wq_m0_at(int nq, int it, int M) { return wq_dma_at(nq, it, M + 1); }
-// a lane offset no tile's descriptor covers: the bounds-checked load writes zeros and fetches nothing
-constexpr int kWqNoFetch = 0x7ffffff0;
 
 // the bounds-checked buffer descriptor of one K or V tile (rows past the tile's last key read as zero)
 __device__ __forceinline__ u32x4 tile_rsrc(const char* base, int64_t sl, int rows) {
@@ -137,6 +151,13 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   constexpr int VB0 = 2 * kBuf;            // K buffers 0, 1, then V buffers 0, 1
   static_assert(4 * kBuf <= 163840, "the CU's LDS");
   __shared__ __attribute__((aligned(16))) char smem[4 * kBuf];
+  // the last piece of the last image of the last buffer (wave 3, j = 3) ends inside smem
+  static_assert(kWqPad || 3 * kBuf + (kIT - 1) * kWqImg + wqimg::piece_dst(wqimg::wave_piece(3, 3)) +
+                                  wqimg::kPieceBytes <= 4 * kBuf,
+                "every DMA piece lands inside smem");
+  static_assert(kWqPad || (wqimg::piece_dst(wqimg::wave_piece(1, 0)) == kWqPieceAt &&
+                           wqimg::piece_dst(wqimg::wave_piece(0, 1)) == kWqPieceStep),
+                "a wave's piece destinations: base + step j");
   constexpr bool kInit = kMode != 1;  // the shift rides in the Q K^T chains' initial C
   constexpr int kPar = kIT == 1 ? 1 : 0;  // iteration T reads the K buffer (T + kPar) & 1 and the V buffer T & 1
   constexpr int kND = wq_dma_n(kIT);
@@ -166,26 +187,37 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   const char* const kbase = (const char*)(a.k + b * a.k_sb + h * a.k_sh + (int64_t)key0 * a.k_sl);
   const char* const vbase = (const char*)(a.v + b * a.v_sb + h * a.v_sh + (int64_t)key0 * a.v_sl);
 
-  // ---- LDS-DMA: piece p of a 64-key image (18 per image) is image bytes [1024 p, +1024) of the 64 x 288-B image, lane
-  // l the 16 B at 16 l of it: row bb / 288, column bb % 288, attn_fwd_m16's dma_tile. Every wave moves the pieces
-  // wave + 4 j, j = 0..3; the fifth offset is piece 16 + (wave & 1): of image 0 on waves 0-1 and of image 1 on waves
-  // 2-3, so a wave moves 9 pieces of the two images of a buffer (one tile per iteration: piece 16 + wave on waves 0-1).
-  // Bounds-checked buffer loads: rows past the tile's last key (the ragged tile, the virtual tiles past Lk) read as
-  // zero. The lanes of the row padding (columns >= 256, which no fragment read touches: K reads and the transposed V
-  // reads end at byte 255 of a row) re-read the tile's first 16 B (lab: an offset outside every descriptor).
+  // ---- LDS-DMA: piece P of a 64-key image (16 per image) goes to image byte 1056 P, lane l bringing the 16 B at
+  // byte column 16 (l & 15) of the tile's row 32 (P >> 3) + (P & 7) + 8 (l >> 4) (attn_wq_image.h). Every wave moves
+  // the pieces wave + 4 j, j = 0..3, of every image: four lane offsets per operand.
+  // Bounds-checked buffer loads, checked per lane: rows past the tile's last key (the ragged tile, which may end
+  // between the four rows of a piece, and the virtual tiles past Lk) read as zero.
+  // The pad image (lab): piece p of 18 is image bytes [1024 p, +1024) of the 64 x 288-B image, lane l the 16 B at 16 l
+  // of it: row bb / 288, column bb % 288, attn_fwd_m16's dma_tile; the lanes of the row padding (columns >= 256, which
+  // no fragment read touches) re-read the tile's first 16 B. The fifth offset is piece 16 + (wave & 1): of image 0 on
+  // waves 0-1 and of image 1 on waves 2-3, so a wave moves 9 pieces of the two images of a buffer (one tile per
+  // iteration: piece 16 + wave on waves 0-1).
   const int wave5 = kIT == 1 ? wave : (wave & 1);  // the fifth piece's lane block
   const int img5 = kIT == 1 ? 0 : (wave >> 1);     // and its image
-  int dk[5], dv[5];
+  int dk[kWqOffs], dv[kWqOffs];
 #pragma unroll
-  for (int j = 0; j < 5; ++j) {
-    const int bb = 1024 * ((j < 4 ? wave : wave5) + 4 * j) + 16 * lane;
-    const int row = bb / kKStride16, cb = bb - row * kKStride16;
-    dk[j] = cb < 2 * kD ? row * (int)(a.k_sl * 2) + cb : (kWqPadFetch ? 0 : kWqNoFetch);
-    dv[j] = cb < 2 * kD ? row * (int)(a.v_sl * 2) + cb : (kWqPadFetch ? 0 : kWqNoFetch);
+  for (int j = 0; j < kWqOffs; ++j) {
+    if constexpr (kWqPad) {
+      const int bb = 1024 * ((j < 4 ? wave : wave5) + 4 * j) + 16 * lane;
+      const int row = bb / kKStride16, cb = bb - row * kKStride16;
+      dk[j] = cb < 2 * kD ? row * (int)(a.k_sl * 2) + cb : 0;
+      dv[j] = cb < 2 * kD ? row * (int)(a.v_sl * 2) + cb : 0;
+    } else {
+      const int P = wqimg::wave_piece(wave, j);
+      const int row = wqimg::piece_row(P, lane), cb = wqimg::piece_col(lane);
+      dk[j] = row * (int)(a.k_sl * 2) + cb;
+      dv[j] = row * (int)(a.v_sl * 2) + cb;
+    }
   }
-  const unsigned lds_wave = (unsigned)(uintptr_t)(lds_char_ptr)smem + 1024u * (unsigned)wave;
-  // the fifth piece's destination: byte 16384 + 1024 (wave & 1) of image img5 (the 16384 rides in the M0 add)
-  const unsigned lds_wave5 =
+  const unsigned lds_wave = (unsigned)(uintptr_t)(lds_char_ptr)smem + (unsigned)kWqPieceAt * (unsigned)wave;
+  // the pad image's fifth piece's destination: byte 16384 + 1024 (wave & 1) of image img5 (the 16384 rides in the M0
+  // add)
+  [[maybe_unused]] const unsigned lds_wave5 =
       (unsigned)(uintptr_t)(lds_char_ptr)smem + 1024u * (unsigned)wave5 + (unsigned)kWqImg * (unsigned)img5;
   auto k_rsrc = [&](int t) __attribute__((always_inline)) {
     return tile_rsrc(kbase + (int64_t)t * kKBlk * a.k_sl * 2, a.k_sl, min(Lk - t * kKBlk, kKBlk));
@@ -211,12 +243,17 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   // prologue: pieces 0-15 of one image whose LDS byte offset is at (every wave its four)
   auto dma_img = [&](const u32x4& rs, const int* offs, unsigned at) __attribute__((always_inline)) {
     static_for<4>([&](auto JC) __attribute__((always_inline)) {
-      dma_piece(rs, offs[decltype(JC)::value], lds_wave + at, std::integral_constant<int, 4096 * decltype(JC)::value>{});
+      dma_piece(rs, offs[decltype(JC)::value], lds_wave + at,
+                std::integral_constant<int, kWqPieceStep * decltype(JC)::value>{});
     });
   };
-  // prologue: the kIT images of the buffer at LDS byte offset at, tiles t0 .. t0 + kIT - 1, with their pieces 16-17
+  // prologue: the kIT images of the buffer at LDS byte offset at, tiles t0 .. t0 + kIT - 1 (the pad image: with their
+  // pieces 16-17)
   auto dma_buf = [&](auto rsrc, const int* offs, int t0, unsigned at) __attribute__((always_inline)) {
-    if constexpr (kIT == 1) {
+    if constexpr (!kWqPad) {
+#pragma unroll
+      for (int i = 0; i < kIT; ++i) dma_img(rsrc(t0 + i), offs, at + (unsigned)(i * kWqImg));
+    } else if constexpr (kIT == 1) {
       const u32x4 rs = rsrc(t0);
       dma_img(rs, offs, at);
       if (wave < 2) dma_piece(rs, offs[4], lds_wave + at, std::integral_constant<int, 16384>{});
@@ -237,7 +274,8 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
     const u32x4 rs = k_rsrc(0);
     dma_img(rs, dk, kK0At);
     // (waves 0-1: lds_wave5 of image 0 is lds_wave)
-    if (wave < 2) dma_piece(rs, dk[4], lds_wave + kK0At, std::integral_constant<int, 16384>{});
+    if constexpr (kWqPad)
+      if (wave < 2) dma_piece(rs, dk[kWqOffs - 1], lds_wave + kK0At, std::integral_constant<int, 16384>{});
   }
   dma_buf(k_rsrc, dk, 1, (unsigned)((kPar & 1) * kBuf));
   dma_buf(v_rsrc, dv, 0, (unsigned)VB0);
@@ -381,9 +419,14 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   typedef short s16x8v __attribute__((ext_vector_type(8)));
   bf16x8 ones8 = __builtin_bit_cast(bf16x8, s16x8v{0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80});
   asm volatile("s_nop 2" : "+a"(ones8));
-  const unsigned k_rd_lds = (unsigned)(uintptr_t)(lds_char_ptr)(smem + c16 * kKStride16 + 16 * g);
+  // the fragment reads' lane bases: row c16, bytes 16 g of a K image; row 4 g + (c16 >> 2), bytes 8 (c16 & 3) of a V
+  // image (lane = 16 g + c16)
+  const unsigned k_rd_lds =
+      (unsigned)(uintptr_t)(lds_char_ptr)smem +
+      (unsigned)(kWqPad ? c16 * kKStride16 + 16 * g : wqimg::k_lane_base(lane));
   const unsigned v_rd_lds =
-      (unsigned)(uintptr_t)(lds_char_ptr)(smem + VB0 + (4 * g + (c16 >> 2)) * kVStride16 + 8 * (c16 & 3));
+      (unsigned)(uintptr_t)(lds_char_ptr)smem + (unsigned)VB0 +
+      (unsigned)(kWqPad ? (4 * g + (c16 >> 2)) * kVStride16 + 8 * (c16 & 3) : wqimg::v_lane_base(lane));
 
   f32x4 S[2][2][kNQ];  // S^T of two half stages: [half-stage parity][key block of the half][query block]
   bf16x8 P[2][kNQ];    // P^T of two half stages: [half-stage parity][query block]
@@ -405,13 +448,17 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
     (void)v_cur;
     if constexpr (f >= 8) {
       constexpr int j = f - 8;
-      constexpr int off = img + (2 * hs + (j & 1)) * 16 * kKStride16 + 64 * (j >> 1);
+      constexpr int kb = 2 * hs + (j & 1), s = j >> 1;
+      constexpr int off = img + (kWqPad ? kb * 16 * kKStride16 + 64 * s : wqimg::k_imm(kb, s));
+      static_assert(off < 65536, "ds_read offset field");
       asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[slot]) : "v"(k_cur), "i"(off));
     } else {
-      constexpr int off = img + 32 * hs * kVStride16 + 32 * f;
+      constexpr int off = img + (kWqPad ? 32 * hs * kVStride16 + 32 * f : wqimg::v_imm(hs, 0, f));
+      constexpr int off_hi = img + (kWqPad ? (32 * hs + 16) * kVStride16 + 32 * f : wqimg::v_imm(hs, 1, f));
+      static_assert(off_hi < 65536, "ds_read offset field");
       s16x4 lo, hi;
       asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(v_cur), "i"(off));
-      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(v_cur), "i"(off + 16 * kVStride16));
+      asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(v_cur), "i"(off_hi));
       typedef short s16x8 __attribute__((ext_vector_type(8)));
       const s16x8 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       ring[slot] = __builtin_bit_cast(bf16x8, r);
@@ -436,11 +483,13 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
   };
 
   // The DMA's wave-uniform state (SGPRs): the descriptors of the tiles iteration t fetches, K(kIT (t + 1) + 1 + i) and
-  // V(kIT (t + 1) + i), i < kIT (rk5 / rv5: the fifth piece's image). Past the last tile: an empty range, the pieces
-  // land as zeros. The product computes them at the head of the iteration. The lab form (kWqHeadRsrc false) makes them
-  // by adds from a running base and row count in three steps, which the loop takes for iteration t + 1 in the last three
-  // gaps of iteration t (they carry nothing else), so that the SALU work sits under MFMAs.
-  u32x4 rk[kIT], rv[kIT], rk5 = {0u, 0u, 0u, 0u}, rv5 = {0u, 0u, 0u, 0u};
+  // V(kIT (t + 1) + i), i < kIT (the pad image's rk5 / rv5: the fifth piece's image). Past the last tile: an empty
+  // range, the pieces land as zeros. The product makes them by adds from a running base and row count in steps, which
+  // the loop takes for iteration t + 1 in the last three gaps of iteration t (they carry nothing else), so that the
+  // SALU work sits under MFMAs. The lab form (kWqHeadRsrc) computes them at the head of the iteration, behind the
+  // barrier with no MFMA in flight.
+  u32x4 rk[kIT], rv[kIT];
+  [[maybe_unused]] u32x4 rk5 = {0u, 0u, 0u, 0u}, rv5 = {0u, 0u, 0u, 0u};
   const int64_t kstep = (int64_t)kKBlk * a.k_sl * 2, vstep = (int64_t)kKBlk * a.v_sl * 2;
   const char* kp = kbase + (kIT + 1) * kstep;
   const char* vp = vbase + kIT * vstep;
@@ -457,7 +506,7 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
       for (int i = 0; i < kIT; ++i) rv[i] = tile_rsrc(vp + i * vstep, a.v_sl, min(rows_v - i * kKBlk, kKBlk));
       vp += kIT * vstep;
       rows_v -= kIT * kKBlk;
-    } else if constexpr (kIT == 2) {
+    } else if constexpr (kWqPad && kIT == 2) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         rk5[e] = img5 ? rk[kIT - 1][e] : rk[0][e];
@@ -495,14 +544,14 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
           rk[i] = k_rsrc(kIT * (t + 1) + 1 + i);
           rv[i] = v_rsrc(kIT * (t + 1) + i);
         }
-        if constexpr (kIT == 2) dma_next(std::integral_constant<int, 2>{});
+        if constexpr (kWqPad && kIT == 2) dma_next(std::integral_constant<int, 2>{});
       }
       // the next iteration's tiles go into the two buffers the previous iteration read
       const unsigned at_k = ((t + 1 + kPar) & 1) ? (unsigned)kBuf : 0u;
       const unsigned at_v = (unsigned)VB0 + (((t + 1) & 1) ? (unsigned)kBuf : 0u);
       dst_k = lds_wave + at_k;
       dst_v = lds_wave + at_v;
-      if constexpr (kIT == 2) {  // pieces 16-17: of image 0 on waves 0-1, of image 1 on waves 2-3
+      if constexpr (kWqPad && kIT == 2) {  // pieces 16-17: of image 0 on waves 0-1, of image 1 on waves 2-3
         dst_k5 = lds_wave5 + at_k;
         dst_v5 = lds_wave5 + at_v;
       }
@@ -518,10 +567,10 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
       (void)dst_v;
       (void)dst_k5;
       (void)dst_v5;
-      if constexpr (kIT == 1) {
+      if constexpr (kWqPad && kIT == 1) {
         if (i < 4 || wave < 2) set_m0(isk ? dst_k : dst_v, std::integral_constant<int, 4096 * i>{});
-      } else if constexpr (i < 8) {
-        set_m0(isk ? dst_k : dst_v, std::integral_constant<int, (i / 4) * kWqImg + 4096 * (i % 4)>{});
+      } else if constexpr (i < 4 * kIT) {  // piece j = i % 4 of image i / 4
+        set_m0(isk ? dst_k : dst_v, std::integral_constant<int, (i / 4) * kWqImg + kWqPieceStep * (i % 4)>{});
       } else {
         set_m0(isk ? dst_k5 : dst_v5, std::integral_constant<int, 16384>{});
       }
@@ -533,12 +582,12 @@ __global__ void __launch_bounds__(kWqThreads, 1) attn_fwd_wq(AttnArgs a) {
       (void)rv;
       (void)rk5;
       (void)rv5;
-      if constexpr (kIT == 1) {
+      if constexpr (kWqPad && kIT == 1) {
         if (i < 4 || wave < 2) dma_load(isk ? rk[0] : rv[0], isk ? dk[i] : dv[i]);
-      } else if constexpr (i < 8) {
+      } else if constexpr (i < 4 * kIT) {
         dma_load(isk ? rk[i / 4] : rv[i / 4], isk ? dk[i % 4] : dv[i % 4]);
       } else {
-        dma_load(isk ? rk5 : rv5, isk ? dk[4] : dv[4]);
+        dma_load(isk ? rk5 : rv5, isk ? dk[kWqOffs - 1] : dv[kWqOffs - 1]);
       }
     };
     static_for<kAheadWq>([&](auto IC) __attribute__((always_inline)) {
