@@ -6,9 +6,9 @@
 //                      text decoder layers (reason1/networks/qwen2_5_vl.py) for a text-only prompt without a padding
 //                      mask (text_encoders/text_encoder.py:186-189).
 //
-// A plain kernel: it is under 1 % of the encoder's FLOPs. Its data path is attn_na.hip's, whose fragment layouts the
-// sparse-attention tests pin: one workgroup = 2 waves = one 64-row query block of one (batch, query head); each wave
-// owns 32 query rows and the whole head dim.
+// A plain kernel: it is under 1 % of the encoder's FLOPs. Its data path is attn_na.hip's, whose fragment layouts
+// tests/test_sparse_attn_exact_gpu.py pins element by element: one workgroup = 2 waves = one 64-row query block of
+// one (batch, query head); each wave owns 32 query rows and the whole head dim.
 //   * swapped products: S^T = K Q^T (v_mfma_f32_32x32x16_bf16, 8 k-steps over d; the query on the lane, its Q^T
 //     fragments loaded once into 32 VGPRs), then O^T = V^T P^T with the S accumulators converted to bf16 in place as the
 //     B operand and V^T read by ds_read_b64_tr_b16; O^T is 4 d-blocks of 32 x 32;
